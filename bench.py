@@ -9,6 +9,24 @@ on a 1024 x 1024 synthetic grid per GPU (BASELINE.json configs[2]; the metric
 resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--grid G]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up
+the context, brings the GPU to its working clock with ~0.1 s of the loop's own
+launches (then resets belief and values), runs the W warm-up steps, times the
+K steps, writes the outputs if asked and prints the result line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload's
+`config`).  --dump-outputs DIR writes what the timed steps left -- the belief,
+the Bellman values and the actions a caller reads back after the last timed
+step -- as DIR/belief.npy, values.npy and actions.npy (float32; N > 1: each
+rank its own rows, `<name>_rank<r>.npy`).  Grid, trajectory and initial state
+are seeded, so the same arguments give the same arrays on every run and build.
+
+Every other leg runs only with --full: the per-kernel timings, the FIB sweep,
+the dense path, the MDP solve, the event-timed rerun behind `roofline`,
+config4, the weak-scaling share, the plan steps, PBVI, the rollout and the CPU
+baselines; everything below about those legs and their keys of the result
+line describes a --full run.
 
 For N > 1 launch with torch.distributed.run, or run it directly: without a
 launcher environment `bench.py --gpus N` starts `torch.distributed.run
@@ -25,7 +43,7 @@ efficiency, tools/weak_shard_rows.py).  --grid G
 (strong scaling): one fixed G x G grid, rows split as evenly as possible over
 the N ranks.
 
-Every run also reports `config4` (BASELINE.json configs[3]): the 2048 x 2048
+A --full run also reports `config4` (BASELINE.json configs[3]): the 2048 x 2048
 grid row-sharded over all N ranks (strong scaling), its cells/s, the same
 grid unsharded on rank 0's GPU in the same job (speedup), and a parity gate:
 the sharded J / A gathered to rank 0 equal the unsharded run bit for bit and
@@ -116,7 +134,14 @@ def parse(argv=None):
     ap.add_argument("--dense", action="store_true",
                     help="time the dense-plane kernels as the main loop")
     ap.add_argument("--profile", action="store_true",
-                    help="only run warmup+timed steps (for rocprofv3)")
+                    help="stop after the timed steps (for rocprofv3; with --full the "
+                         "per-kernel legs before the warm-up still run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (per-kernel timings, rooflines, "
+                         "config4, plan steps, PBVI, rollout, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the belief, values and actions left by the last timed "
+                         "step as DIR/<name>.npy (float32)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="ranks join a gloo group, all-reduce one value and rank 0 prints "
                          "one JSON line; nothing touches a GPU (tests the N > 1 launch)")
@@ -924,6 +949,51 @@ def cpu_model():
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs writes at most this much
+CLOCK_WARM_MS = 100.0            # busy time that brings an idle GPU to its working clock
+
+
+def dump_outputs(dirname, arrays, suffix="", limit=DUMP_LIMIT_BYTES):
+    """Write each of `arrays` ({name: array}) as dirname/<name><suffix>.npy in
+    float32 (float64 stays float64).  Together they take at most `limit`
+    bytes: an array over its equal share of the limit is cut to a fixed
+    sample, the sorted indices drawn by default_rng(0) for that length, the
+    same on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+        path = os.path.join(dirname, f"{name}{suffix}.npy")
+        np.save(path, a, allow_pickle=False)
+        written[name] = int(a.size)
+    return written
+
+
+def clock_warm(ctx, us, zs, collective=False, ms=CLOCK_WARM_MS):
+    """Keep the GPU busy for ~`ms` with the loop's own launches, back to back.
+    A GPU fresh out of idle runs the same launch ~8 % slower
+    (tools/micro/clock_warmup.py, profiles/r03/clock_warmup.txt); a --full
+    run gets this from its per-kernel legs.  The caller resets belief and
+    values afterwards.  Row shards (`collective`) run a fixed 64 launches
+    instead: every rank must issue the same RCCL rounds."""
+    n = min(200, len(us))
+    if n == 0:
+        return
+    t0 = time.perf_counter()
+    rounds = 0
+    while (rounds < 8) if collective else ((time.perf_counter() - t0) * 1e3 < ms):
+        for _ in range(8):
+            ctx.loop_run(us[:n], zs[:n])
+        ctx.synchronize()
+        rounds += 1
+
+
 def main():
     args = parse()
     ws, rank, local = dist_env()
@@ -989,7 +1059,7 @@ def main():
     ctx.synchronize()
 
     # ------------------------------------------- per-kernel timing (HIP events)
-    # These secondary legs run BEFORE the headline's warmup and timed steps:
+    # These secondary legs (--full only) run BEFORE the headline's warmup and timed steps:
     # they keep the GPU busy for tens of ms, so the timed steps run at the
     # working clock (a GPU fresh out of idle runs the same 20-step launch
     # ~8 % slower, tools/micro/clock_warmup.py).  The state is reset after.
@@ -1008,18 +1078,22 @@ def main():
     def loop_reps():
         ctx.loop_run(us[:reps], zs[:reps])
 
-    sweep_ms = timed(lambda: ctx.mdp_sweep(reps))  # coded when active
-    pairs_ms = None
-    if coded and steps_per_launch >= RESIDENT_STEPS:
-        # the launch-per-pair path beside the resident loop (same steps)
-        ctx.set_tuning(ctx.TUNE_RESIDENT, 0)
-        pairs_ms = timed(loop_reps)
-        ctx.set_tuning(ctx.TUNE_RESIDENT, 1)
-    belief_ms = timed(lambda: [ctx.belief_update(int(us[k]), int(zs[k])) for k in range(reps)])
+    pairs_ms = fib = dense = mdp_solve = None
+    if not args.full:
+        # a plain run: no secondary leg, only the working clock they would leave
+        clock_warm(ctx, us, zs, collective=ws > 1)
+    if args.full:
+        sweep_ms = timed(lambda: ctx.mdp_sweep(reps))  # coded when active
+        if coded and steps_per_launch >= RESIDENT_STEPS:
+            # the launch-per-pair path beside the resident loop (same steps)
+            ctx.set_tuning(ctx.TUNE_RESIDENT, 0)
+            pairs_ms = timed(loop_reps)
+            ctx.set_tuning(ctx.TUNE_RESIDENT, 1)
+        belief_ms = timed(lambda: [ctx.belief_update(int(us[k]), int(zs[k]))
+                                   for k in range(reps)])
     # row a5: the FIB sweep on the same grid (VALU-bound: SURVEY.md §8(d)
     # prices it on the reference's full-sum flops against the f32 VALU peak)
-    fib = None
-    if rank == 0 and ws == 1:
+    if args.full and rank == 0 and ws == 1:
         ctx.fib_reset()
         ctx.fib_sweep(3)
         fib_ms = timed(lambda: ctx.fib_sweep(reps))
@@ -1032,8 +1106,7 @@ def main():
                "note": "flops of the reference's full 9-term sums (SURVEY.md §8(d), ~25.9 "
                        "kflop/cell); the kernel executes the support terms only (~11.5 k), "
                        "bit-identical"}
-    dense = None
-    if coded:
+    if args.full and coded:
         ctx.set_tuning(ctx.TUNE_CODED_MODEL, 0)
         dloop_ms = timed(loop_reps)
         dsweep_ms = timed(lambda: ctx.mdp_sweep(reps))
@@ -1050,8 +1123,7 @@ def main():
                  "mdp_sweep_us": dsweep_ms * 1e3,
                  "mdp_sweep_frac": BYTES_SWEEP * cells_per_gpu / (dsweep_ms * 1e-3) / 1e9
                  / HBM_PEAK_GBS}
-    mdp_solve = None
-    if rank == 0 and ws == 1:
+    if args.full and rank == 0 and ws == 1:
         # BASELINE configs[2]: MDP value iteration to convergence on this grid
         # (valueIteration, src/mdp/path_planning_2d.cu:207-269, no GUI)
         # the first solve on a context also pays its one-time setup (the
@@ -1105,9 +1177,17 @@ def main():
     value = gh * gw * args.steps / elapsed
     # sanity: the belief is still a distribution (checks the timed work ran)
     mass_ok = None
+    b_out = None
+    if (rank == 0 and ws == 1) or args.dump_outputs:  # (N > 1: belief_get is collective)
+        b_out = ctx.belief_get()
     if rank == 0 and ws == 1:
-        bsum = float(ctx.belief_get().astype(np.float64).sum())
+        bsum = float(b_out.astype(np.float64).sum())
         mass_ok = abs(bsum - 1.0) < 1e-4
+    if args.dump_outputs:
+        # what the timed steps left, before any later leg advances the state
+        J_out, A_out = ctx.mdp_get()
+        dump_outputs(args.dump_outputs, {"belief": b_out, "values": J_out, "actions": A_out},
+                     suffix=f"_rank{rank}" if ws > 1 else "")
 
     if args.profile:
         if rank == 0:
@@ -1115,6 +1195,50 @@ def main():
                               "ms_per_step": 1e3 * elapsed / args.steps}))
         ctx.close()
         if ws > 1:
+            dist.destroy_process_group()
+        return
+
+    head = {
+        "metric": "grid cells/sec for belief-update+Bellman loop, 1024x1024; plan step p50 ms",
+        "value": value,
+        "unit": "cells/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "full": bool(args.full),
+        "data": "synthetic: splitmix64 occupancy grid (p_occ=0.2, seed=H), "
+                "uniform initial belief, seeded simulated (u,z) trajectory",
+        "config": {
+            "workload": (f"{gh}x{gw} grid row-sharded over {ws} GPU(s): 1 belief update + "
+                         f"1 MDP Bellman sweep per step" if strong else
+                         f"{r1 - r0}x{args.size} cells per GPU: 1 belief update + 1 MDP "
+                         f"Bellman sweep per step (BASELINE.json configs[2] grid"
+                         + (")" if ws == 1 else f"; {r1 - r0}-row shards so that each "
+                            f"rank's view with its halo rows is one tile per CU)")),
+            "grid": [gh, gw],
+            "rows_per_gpu": r1 - r0,
+            "parallelism": (f"row-shard x{ws}: tile-resident launches of up to e steps, "
+                            f"each after one RCCL exchange of e halo rows and a "
+                            f"{{mass, shift}} all-reduce (e = {(args.size - (r1 - r0)) // 2})"
+                            if ws > 1 else "single GPU"),
+            "cells_per_lane": args.cpt,
+            "model": (f"dictionary-coded ({dict_entries} entries, uint16 code per cell)"
+                      if coded else "dense fp32 planes"),
+        },
+        "belief_mass_ok": mass_ok,
+    }
+    if not args.full:
+        # a plain run ends here: the headline and nothing that takes a run of its own
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(head))
+        if ws > 1:
+            dist.barrier()
             dist.destroy_process_group()
         return
 
@@ -1200,36 +1324,7 @@ def main():
         if ws == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(grid, goal, us, zs, args.cpu_seconds)
         result = {
-            "metric": "grid cells/sec for belief-update+Bellman loop, 1024x1024; plan step p50 ms",
-            "value": value,
-            "unit": "cells/s",
-            "n_gpus": ws,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic: splitmix64 occupancy grid (p_occ=0.2, seed=H), "
-                    "uniform initial belief, seeded simulated (u,z) trajectory",
-            "config": {
-                "workload": (f"{gh}x{gw} grid row-sharded over {ws} GPU(s): 1 belief update + "
-                             f"1 MDP Bellman sweep per step" if strong else
-                             f"{r1 - r0}x{args.size} cells per GPU: 1 belief update + 1 MDP "
-                             f"Bellman sweep per step (BASELINE.json configs[2] grid"
-                             + (")" if ws == 1 else f"; {r1 - r0}-row shards so that each "
-                                f"rank's view with its halo rows is one tile per CU)")),
-                "grid": [gh, gw],
-                "rows_per_gpu": r1 - r0,
-                "parallelism": (f"row-shard x{ws}: tile-resident launches of up to e steps, "
-                                f"each after one RCCL exchange of e halo rows and a "
-                                f"{{mass, shift}} all-reduce (e = {(args.size - (r1 - r0)) // 2})"
-                                if ws > 1 else "single GPU"),
-                "cells_per_lane": args.cpt,
-                "model": (f"dictionary-coded ({dict_entries} entries, uint16 code per cell)"
-                          if coded else "dense fp32 planes"),
-            },
+            **head,
             "roofline": {
                 "kernel": (f"{loop_kernel} (the whole timed trajectory, {args.steps} fused loop "
                            f"steps, in one launch: one tile of rows per CU resident in LDS)"
@@ -1321,7 +1416,6 @@ def main():
                         "timed steps run at the GPU's working clock; a GPU fresh out of idle "
                         "runs the same 20-step launch ~8 % slower (tools/micro/clock_warmup.py, "
                         "profiles/r03/clock_warmup.txt)"},
-            "belief_mass_ok": mass_ok,
             "mdp_solve": mdp_solve,
             "plan_step": plan,
             "rollout": rollout,

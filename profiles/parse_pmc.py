@@ -1,4 +1,4 @@
-"""Summarise a rocprofv3 run of `bench.py --profile` into profiles/pmc_<tag>.json.
+"""Summarise a rocprofv3 run of `bench.py --full --profile` into profiles/pmc_<tag>.json.
 
 Inputs (merged back from the GPU box by gpurun): gpurun_out/prof/
 run_kernel_stats.csv (kernel durations), gpurun_out/pmc_fetch/ and
@@ -71,7 +71,7 @@ def main():
                 d["hbm_over_algorithmic"] = d["hbm_bytes_per_launch"] / d["algorithmic_bytes_per_launch"]
         kernels[k] = d
     res = {"tag": tag, "source": "rocprofv3 --kernel-trace --stats; --pmc FETCH_SIZE; --pmc WRITE_SIZE "
-                               "(separate passes) of `python3 bench.py --profile`",
+                               "(separate passes) of `python3 bench.py --full --profile`",
            "hbm_bytes_formula": "(2*FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950 FETCH_SIZE half-count correction)",
            "kernels": kernels}
     path = os.path.join(ROOT, "profiles", f"pmc_{tag}.json")

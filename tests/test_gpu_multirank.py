@@ -31,7 +31,8 @@ def test_two_rank_rccl_config4_parity():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     # no launcher: bench.py itself starts torch.distributed.run as a child
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16",
+    # --full: the config4 leg and the event-timed RCCL rounds are not part of a plain run
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "16",
            "--warmup", "8", "--c4-steps", "24", "--c4-warmup", "8", "--kernel-reps", "8",
            "--plan-steps", "0", "--no-pbvi", "--rollout-copies", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=100)

@@ -8,7 +8,7 @@ OUT=gpurun_out/ab_bench20.txt
 : > $OUT
 for rep in 1 2 3; do
   for lib in path_planning_2d_amd/libpp2_hip.so tools/_var/*.so; do
-    PP2_LIBRARY=$PWD/$lib timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 \
+    PP2_LIBRARY=$PWD/$lib timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 \
       --no-cpu-baseline --no-pbvi --plan-steps 0 --rollout-copies 0 --c4-size 0 --shard-rows 0 \
       > gpurun_out/ab_b.json 2> gpurun_out/ab_b.err || exit 1
     python3 -c "

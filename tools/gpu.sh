@@ -3,7 +3,7 @@
 # ROUND (default r06) names the PMC summary directories.
 #   tests    full `pytest -m gpu` suite
 #   planner  tests/test_gpu_planner.py only
-#   bench    driver-style bench (N=1, 20 steps)
+#   bench    the bench with every leg (--full, N=1, 20 steps)
 #   prof     rocprofv3 kernel trace of the bench's timed loop + the plan-step legs
 #   pmc      HBM counters of the resident loop / solve (tools/collect_pmc.sh)
 #   fchain   tests/test_gpu_fchain.py (the exact chain sets, FC_LIST included)
@@ -32,8 +32,8 @@ T="--timeout 150 --timeout-method thread -p no:cacheprovider"
 run_tests()   { timeout -k 10 900 python -u -m pytest tests -m gpu -x -v $T > $OUT/pytest_gpu.log 2>&1; }
 run_planner() { timeout -k 10 600 python -u -m pytest tests/test_gpu_planner.py -x -v $T > $OUT/pytest_planner.log 2>&1; }
 run_smoke()   { timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; }
-run_bench()   { timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; }
-run_prof()    { timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --profile --steps 20 --warmup 20 > $OUT/prof.log 2>&1; }
+run_bench()   { timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; }
+run_prof()    { timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --profile --steps 20 --warmup 20 > $OUT/prof.log 2>&1; }
 run_pmc()     { PMC_DIR=pmc_${ROUND:-r06} timeout -k 10 900 bash tools/collect_pmc.sh > $OUT/pmc.log 2>&1; }
 run_pmcx()    { PP2_LIBRARY=$PWD/tools/_var/c_xcd.so PMC_DIR=pmc_${ROUND:-r06}x timeout -k 10 900 bash tools/collect_pmc.sh > $OUT/pmcx.log 2>&1; }
 run_shards()  { timeout -k 10 600 python -u -m pytest tests/test_gpu_shards.py tests/test_gpu_resident.py -x -v $T > $OUT/pytest_shards.log 2>&1; }
