@@ -162,6 +162,95 @@ __device__ __forceinline__ void coded_sweep_iw(const float* sTC, const uint32_t 
   }
 }
 
+// The software-pipelined form of the same backup (the resident loop's
+// whole-row instance and the resident sweep): action-outer over the lane's N
+// cells with two record buffers -- the {quad, cost} records of action a + 1
+// (5 VGPRs per cell) are issued before the fmaf chain and min of action a, so
+// a wave's table reads land under its own VALU work instead of in a drain per
+// cell; the waits are the compiler's counted lgkmcnt(N) (LDS returns in
+// order).  The DS-read / VALU group barriers pin that interleave per cell:
+// {offset of (a + 1, k)}, {its two reads}, {fmafs and min of (a, k)}.
+// Per cell the same fmaf chain and ascending action order as the cell-outer
+// form, so the results are its results bit for bit.
+template <int N, bool ARG, int A>
+__device__ __forceinline__ void sweep_pipe_action(const char* qt, const char* ct,
+                                                  const uint32_t (&iw)[N][3],
+                                                  const float (&jn)[9][N], float (&tv)[2][N][4],
+                                                  float (&cost)[2][N], float (&best)[N],
+                                                  uint32_t (&arg)[N]) {
+  constexpr int cur = A & 1, nxt = cur ^ 1, B = A + 1;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    if constexpr (B < 9) {
+      uint32_t w = B < 4 ? iw[k][0] : B < 8 ? iw[k][1] : iw[k][2];
+      // (opaque in the ARG form: otherwise the 36 record addresses, common to
+      // the caller's ARG and values-only branches, are hoisted above the branch
+      // into 36 live VGPRs)
+      if constexpr (ARG) asm volatile("" : "+v"(w));
+      const uint32_t off = __builtin_amdgcn_ubfe(w, 8 * (B % 4), 8);
+      constexpr int tab = B * kFactK * 16;
+      if constexpr (kSupN[B] == 1) {
+        tv[nxt][k][0] = *reinterpret_cast<const float*>(qt + tab + off);
+      } else {
+        const f4a t = *reinterpret_cast<const f4a*>(qt + tab + off);
+        tv[nxt][k][0] = t[0]; tv[nxt][k][1] = t[1]; tv[nxt][k][2] = t[2]; tv[nxt][k][3] = t[3];
+      }
+      cost[nxt][k] = *reinterpret_cast<const float*>(ct + tab + off);
+    }
+    if constexpr (A >= 0) {
+      float c = cost[cur][k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < kSupN[A]) c = __builtin_fmaf(tv[cur][k][j], jn[kSup[A][j]][k], c);
+      if constexpr (ARG) {
+        if (c < best[k]) { best[k] = c; arg[k] = (uint32_t)A; }
+      } else {
+        best[k] = __builtin_fminf(best[k], c);
+      }
+    }
+    if constexpr (B < 9) {
+      __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);  // the record offset of (B, k)
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // its two DS reads
+    }
+    if constexpr (A >= 0)
+      __builtin_amdgcn_sched_group_barrier(0x002, kSupN[A] + (ARG ? 3 : 1), 0);
+  }
+}
+// _begin: the records of action 0 (the caller may put other work between the
+// two halves: they land under it); _rest: the nine actions.
+template <int N, bool ARG>
+__device__ __forceinline__ void coded_sweep_iw_pipe_begin(const float* sTC,
+                                                          const uint32_t (&iw)[N][3],
+                                                          float (&tv)[2][N][4], float (&cost)[2][N],
+                                                          float (&best)[N], uint32_t (&arg)[N]) {
+  const char* qt = reinterpret_cast<const char*>(sTC + kFactQT);
+  const char* ct = reinterpret_cast<const char*>(sTC + kFactCT);
+  const float jn[9][N] = {};  // (unused by the -1 stage)
+#pragma unroll
+  for (int k = 0; k < N; ++k) { best[k] = FLT_MAX; arg[k] = 0; }
+  sweep_pipe_action<N, ARG, -1>(qt, ct, iw, jn, tv, cost, best, arg);
+}
+template <int N, bool ARG>
+__device__ __forceinline__ void coded_sweep_iw_pipe_rest(const float* sTC,
+                                                         const uint32_t (&iw)[N][3],
+                                                         const float (&jn)[9][N],
+                                                         float (&tv)[2][N][4], float (&cost)[2][N],
+                                                         float (&best)[N], uint32_t (&arg)[N]) {
+  const char* qt = reinterpret_cast<const char*>(sTC + kFactQT);
+  const char* ct = reinterpret_cast<const char*>(sTC + kFactCT);
+#define PP2_PA(AA) sweep_pipe_action<N, ARG, AA>(qt, ct, iw, jn, tv, cost, best, arg);
+  PP2_PA(0) PP2_PA(1) PP2_PA(2) PP2_PA(3) PP2_PA(4) PP2_PA(5) PP2_PA(6) PP2_PA(7) PP2_PA(8)
+#undef PP2_PA
+}
+template <int N, bool ARG>
+__device__ __forceinline__ void coded_sweep_iw_pipe(const float* sTC, const uint32_t (&iw)[N][3],
+                                                    const float (&jn)[9][N], float (&best)[N],
+                                                    uint32_t (&arg)[N]) {
+  float tv[2][N][4], cost[2][N];
+  coded_sweep_iw_pipe_begin<N, ARG>(sTC, iw, tv, cost, best, arg);
+  coded_sweep_iw_pipe_rest<N, ARG>(sTC, iw, jn, tv, cost, best, arg);
+}
+
 // Bellman backup of 4 cells from their codes (k_mdp_sweep's arithmetic).
 // ARG = false: values only (the resident loop's intermediate steps store no
 // actions), best = minnum over the actions -- the same value as the strict-<

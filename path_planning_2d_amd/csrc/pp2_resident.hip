@@ -27,6 +27,8 @@
 //     tree, sc1 loads) once the counter is full.  The partials of step t go to
 //     ring slot t % kResidentRing (no tile runs more than one block ahead of
 //     the slowest, so a slot is never rewritten while a block start reads it);
+//     in the whole-row instance only the steps whose slot is read -- the one
+//     before a block start and the last -- compute partials at all;
 //   * the last step stores b, J and A for the whole grid (non-temporal) and its
 //     partials to the context's pending buffer -- b and J into the OTHER
 //     ping-pong buffers, so the run's inputs survive it.
@@ -220,9 +222,30 @@ constexpr bool belief_row_used(int U, int r) {
     if ((TR ? s % 3 : s / 3) == r && sup_slot(U, 8 - s) >= 0) return true;
   return false;
 }
-template <int U, bool TR>
+// PRE: the class dwords of the three plane rows (cm: the lane's own, ce: lanes
+// 0 / 63's edge dwords) are in hand -- load_class_rows, issued by the caller
+// with the window rows so that they cost no LDS round trip of their own.
+struct ClassRows {
+  uint32_t m[3], e[3];
+};
+__device__ __forceinline__ void load_class_rows(const uint8_t* prow, int ps, int x0, ClassRows& c) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int oy = 0; oy < 3; ++oy) {
+    const uint8_t* r = prow + oy * ps + 4 + x0;
+    c.m[oy] = *reinterpret_cast<const uint32_t*>(r);
+    c.e[oy] = 0u;
+  }
+  if (lane == 0 || lane == 63) {
+#pragma unroll
+    for (int oy = 0; oy < 3; ++oy)
+      c.e[oy] = *reinterpret_cast<const uint32_t*>(prow + oy * ps + 4 + x0 + (lane == 0 ? -4 : 4));
+  }
+}
+template <int U, bool TR, bool PRE = false>
 __device__ __forceinline__ void belief_fact(const uint8_t* prow, int ps, int x0, uint32_t lx4,
-                                            int z, const Win6& win, float (&p)[4]) {
+                                            int z, const Win6& win, float (&p)[4],
+                                            const ClassRows* pre = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const char* qr = reinterpret_cast<const char*>(lds + kResQR) + U * kFactK * 16;
   const char* lt = reinterpret_cast<const char*>(lds + kResLT) + z * (kResLK * 4);
@@ -232,10 +255,15 @@ __device__ __forceinline__ void belief_fact(const uint8_t* prow, int ps, int x0,
 #pragma unroll
   for (int oy = 0; oy < 3; ++oy) {
     if (!belief_row_used<TR>(U, oy)) continue;
-    const uint8_t* r = prow + oy * ps + 4 + x0;
-    const uint32_t m = *reinterpret_cast<const uint32_t*>(r);
-    uint32_t e = 0u;
-    if (lane == 0 || lane == 63) e = *reinterpret_cast<const uint32_t*>(r + (lane == 0 ? -4 : 4));
+    uint32_t m, e = 0u;
+    if constexpr (PRE) {
+      m = pre->m[oy];
+      e = pre->e[oy];
+    } else {
+      const uint8_t* r = prow + oy * ps + 4 + x0;
+      m = *reinterpret_cast<const uint32_t*>(r);
+      if (lane == 0 || lane == 63) e = *reinterpret_cast<const uint32_t*>(r + (lane == 0 ? -4 : 4));
+    }
     const uint32_t l = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)m, 0x138, 0xf, 0xf, false);
     const uint32_t h = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)m, 0x130, 0xf, 0xf, false);
     cb[oy][0] = l >> 24;
@@ -377,6 +405,27 @@ __device__ __forceinline__ void belief_any(int u, const uint8_t* sP, int prows, 
     break;
     PP2_BQ(0) PP2_BQ(1) PP2_BQ(2) PP2_BQ(3) PP2_BQ(4) PP2_BQ(5) PP2_BQ(6) PP2_BQ(7)
     default: belief_fact<8, TR>(pu, ps, x0, lx4, z, w, p);
+#undef PP2_BQ
+  }
+}
+// The same from class dwords already in hand (load_class_rows of the plane
+// rows class_rows_of(u, ...), issued by the caller with the window rows).
+__device__ __forceinline__ const uint8_t* class_rows_of(int u, const uint8_t* sP, int prows, int ps,
+                                                        int ty) {
+  int off = (u * prows + ty) * ps;
+  asm("" : "+v"(off));
+  return sP + off;
+}
+template <bool TR>
+__device__ __forceinline__ void belief_any_pre(int u, int x0, uint32_t lx4, int z, const Win6& w,
+                                               const ClassRows& c, float (&p)[4]) {
+  switch (u) {
+#define PP2_BQ(UU)                                                  \
+  case UU:                                                          \
+    belief_fact<UU, TR, true>(nullptr, 0, x0, lx4, z, w, p, &c);    \
+    break;
+    PP2_BQ(0) PP2_BQ(1) PP2_BQ(2) PP2_BQ(3) PP2_BQ(4) PP2_BQ(5) PP2_BQ(6) PP2_BQ(7)
+    default: belief_fact<8, TR, true>(nullptr, 0, x0, lx4, z, w, p, &c);
 #undef PP2_BQ
   }
 }
@@ -591,6 +640,8 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     const ResidentHead a, const Trajectory<CAP> tr) {
   static_assert(!TR || TC == 1, "transposed tiles are whole kernel rows");
   constexpr int kSweepG = TC == 3 ? 4 : TC > 1 ? 2 : 0;
+  // the whole-row instance: the software-pipelined backup (coded_sweep_iw_pipe)
+  constexpr bool kSweepPipe = TC == 1 && !LAG && !TR;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // a tile: rt rows x tw columns (tc tile columns per row of tiles)
   constexpr int tc = TC == 3 ? 2 : TC;
@@ -938,6 +989,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     }
     PP2_RT(0);
     local = 0.0f;
+    // ---- arrive for the next step's block start (below).  Ring slot t is read
+    // only by the block start of step t + 1 and, the last step's, after the
+    // loop, so the whole-row instance computes no mass partial on the other
+    // steps.  (The other instances keep the partial per step: the change was
+    // timed on the whole-row instance only.)
+    const bool arrive = (a.kstep0 + t + 1) % a.depth == 0;
+    const bool mass = !kSweepPipe || arrive || last;
     // one quad of step t: window rows from LDS (step t-1), the neighbour rows
     // of step t-1, or 0 off the grid; b' before the scale in p
     auto step_quad = [&]() {
@@ -945,6 +1003,16 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       float sb[3] = {0.0f, 0.0f, 0.0f}, sj[3] = {0.0f, 0.0f, 0.0f};
       const bool sd = sd_l || sd_r;
       const unsigned bit = use[co] & 1u;
+      // (the whole-row instance) issued with the window rows, so that they
+      // land in the same LDS round trip: the gather's class dwords and the
+      // backup's records of action 0
+      ClassRows crow;
+      if constexpr (kSweepPipe) load_class_rows(class_rows_of(u, sP, prows, ps, ty), ps, x0, crow);
+      float rtv[2][4][4], rcost[2][4];
+      if constexpr (kSweepPipe) {
+        if (last) coded_sweep_iw_pipe_begin<4, true>(sTC, iwr, rtv, rcost, best, arg);
+        else coded_sweep_iw_pipe_begin<4, false>(sTC, iwr, rtv, rcost, best, arg);
+      }
       if (ty > 0) {
         row_lds(sbuf(0, ci) + (ty - 1) * xs, x0, wb.v[0]);
         row_lds(sbuf(1, ci) + (ty - 1) * xs, x0, wj.v[0]);
@@ -988,6 +1056,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         for (int i = 0; i < (kClsSlots + 1) / 2; ++i) asm volatile("" : "+v"(creg.lh[i]));
         belief_any_regs(u, creg, lx4, z, wb, p);
       }
+      else if constexpr (kSweepPipe) belief_any_pre<TR>(u, x0, lx4, z, wb, crow, p);
       else belief_any<TR>(u, sP, prows, ps, ty, x0, lx4, z, wb, p);
       float jn[9][4];  // grid stencil offset i = 3 (dy + 1) + dx + 1
 #pragma unroll
@@ -995,17 +1064,23 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
 #pragma unroll
         for (int k = 0; k < 4; ++k) jn[i][k] = TR ? wj.v[i % 3][k + i / 3] : wj.v[i / 3][k + i % 3];
       // (2-D tiles: the cells' table reads in pairs, coded_sweep_iw)
-      if (last) coded_sweep_iw<4, true, kSweepG>(sTC, iwr, jn, best, arg);  // actions: last step only
-      else coded_sweep_iw<4, false, kSweepG>(sTC, iwr, jn, best, arg);
+      if constexpr (kSweepPipe) {  // (actions: last step only)
+        if (last) coded_sweep_iw_pipe_rest<4, true>(sTC, iwr, jn, rtv, rcost, best, arg);
+        else coded_sweep_iw_pipe_rest<4, false>(sTC, iwr, jn, rtv, rcost, best, arg);
+      } else {
+        if (last) coded_sweep_iw<4, true, kSweepG>(sTC, iwr, jn, best, arg);
+        else coded_sweep_iw<4, false, kSweepG>(sTC, iwr, jn, best, arg);
+      }
       *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) = f4a{best[0], best[1], best[2], best[3]};
     };
     // the scale, the mass partial, b' into LDS and the boundary rows out --
     // the neighbours' next inputs
     auto finish_quad = [&]() {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        p[k] = p[k] * inv;
-        local += p[k];
+      for (int k = 0; k < 4; ++k) p[k] = p[k] * inv;
+      if (mass) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) local += p[k];
       }
       *reinterpret_cast<f4a*>(sbuf(0, co) + ty * xs + x0) = f4a{p[0], p[1], p[2], p[3]};
       if (bnd) {
@@ -1042,14 +1117,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     if (last) break;  // the last step's outputs are stored after the loop
     ++use[ci];
     // ---- mass partials of step t (dense map), sc1 into the ring
-    {
+    if (mass) {
       const float v = wave_sum(local);
       if (lane == 0 && pi < a.nparts)
         st_flag(reinterpret_cast<unsigned*>(a.ring + (size_t)(t % kResidentRing) * a.nparts + pi),
                 __float_as_uint(v));
     }
-    // ---- arrive for the next step's block start (every wave drained first)
-    const bool arrive = (a.kstep0 + t + 1) % a.depth == 0;
+    // ---- (every wave drained before the arrival)
     if (arrive) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (wave == redw && lag_start(t + 1)) {  // the lagged mass for the next step's block start
       float S;
@@ -1218,8 +1292,8 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
       for (int i = 0; i < 9; ++i)
 #pragma unroll
         for (int k = 0; k < 4; ++k) jn[i][k] = w.v[i / 3][k + i % 3];
-      if (check || fin) coded_sweep_iw<4, true>(sTC, iwr, jn, best, arg);
-      else coded_sweep_iw<4, false>(sTC, iwr, jn, best, arg);
+      if (check || fin) coded_sweep_iw_pipe<4, true>(sTC, iwr, jn, best, arg);
+      else coded_sweep_iw_pipe<4, false>(sTC, iwr, jn, best, arg);
       *reinterpret_cast<f4a*>(sbuf(co) + ty * xs + x0) = f4a{best[0], best[1], best[2], best[3]};
       if (nb_up || nb_dn) {
         publish(ci, best, (use[ci] + 1u) & 1u);
