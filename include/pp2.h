@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PP2_ABI_VERSION 3
+#define PP2_ABI_VERSION 4
 
 typedef enum {
   PP2_OK = 0,
@@ -309,6 +309,33 @@ int pp2_mdp_get(pp2_ctx* ctx, float* J, uint8_t* A);
  * Asynchronous. */
 int pp2_loop_step(pp2_ctx* ctx, uint8_t u, uint8_t z);
 int pp2_loop_run(pp2_ctx* ctx, int n, const uint8_t* us, const uint8_t* zs);
+
+/* ---------------------------------------------------------------- control
+ * The next control from the device-resident belief, J and A, without moving a
+ * plane to the host: each call copies one small record back and synchronises.
+ * Unsharded contexts only (a row shard or shard-group member: PP2_ESTATE).
+ *
+ * pp2_belief_mode: the scan of MdpPathPlanning2d::beliefCallback
+ * (src/mdp/path_planning_2d.cu:168-189) over the normalised belief n =
+ * pp2_belief_get: cell = the smallest idx = y*W + x with n(idx) > 0 and
+ * n(idx) >= n(j) for all j, prob = n(cell); cell 0, prob 0 when no cell is
+ * > 0 (NaNs never win).  Either pointer may be NULL. */
+int pp2_belief_mode(pp2_ctx* ctx, int32_t* cell, float* prob);
+/* Belief-expected Q values of the current J (no reference counterpart):
+ * q[u] = (sum_x b(x) Q(x,u)) / mass over the stored belief b and its mass,
+ * Q(x,u) = C[x][u] + sum_i gamma*T[x][u][i] * J(x+off_i) with
+ * pp2_mdp_sweep's arithmetic, J = 0 outside the grid.  Summed in a fixed
+ * order: bit-identical from run to run and between PP2_TUNE_CODED_MODEL 0 and
+ * 1.  Needs a model (else PP2_ESTATE). */
+int pp2_mdp_qvalues(pp2_ctx* ctx, float q[9]);
+/* The control of a policy.  PP2_CONTROL_MODE: cell = pp2_belief_mode's,
+ * action = A[cell], value = J[cell] (the planes of pp2_mdp_get).
+ * PP2_CONTROL_QMDP: action = the first u attaining min_u q[u] (strict <, the
+ * sweep's tie rule), value = q[action], cell = -1.  value and cell may be
+ * NULL.  Needs a model (else PP2_ESTATE); an unknown policy is PP2_EINVAL. */
+#define PP2_CONTROL_MODE 0   /* reference MDP node: action of the belief's mode */
+#define PP2_CONTROL_QMDP 1   /* argmin_u of the belief-expected Q over the current J */
+int pp2_mdp_control(pp2_ctx* ctx, int policy, uint8_t* action, float* value, int32_t* cell);
 
 /* ---------------------------------------------------------------- FIB
  * cudaFIBValueIteration sweeps (fast_informed_bound_cuda.cu:97-204) from the

@@ -8,7 +8,12 @@ package is the Python host mirror of that boundary.
 from ._lib import Pp2Error, LIB_PATH
 from .core import GridContext, ShardGroup, device_count
 from .planner import BatchedRollout, QVTreePlanner
+from .controller import BeliefMdpController
 from . import maps, synthetic
 
-__all__ = ["GridContext", "ShardGroup", "QVTreePlanner", "BatchedRollout", "device_count", "Pp2Error",
-           "LIB_PATH", "maps", "synthetic"]
+CONTROL_MODE = GridContext.CONTROL_MODE
+CONTROL_QMDP = GridContext.CONTROL_QMDP
+
+__all__ = ["GridContext", "ShardGroup", "QVTreePlanner", "BatchedRollout", "BeliefMdpController",
+           "CONTROL_MODE", "CONTROL_QMDP", "device_count", "Pp2Error", "LIB_PATH", "maps",
+           "synthetic"]

@@ -12,7 +12,7 @@ import os
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # PP2_LIBRARY points at a diagnostic build of the same ABI (tools/micro/).
 # include/pp2.h PP2_ABI_VERSION (tests/test_abi.py checks the two agree)
-PP2_ABI_VERSION = 3
+PP2_ABI_VERSION = 4
 LIB_PATH = os.environ.get("PP2_LIBRARY") or os.path.join(PKG_DIR, "libpp2_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "pp2.h")
 
@@ -77,6 +77,9 @@ SIGNATURES = {
     # trajectories go in as bytes objects (c_char_p: a pointer to their
     # buffer, no per-call ctypes array objects -- ~8 us of host time per call)
     "pp2_loop_run": [_vp, C.c_int, C.c_char_p, C.c_char_p],
+    "pp2_belief_mode": [_vp, C.POINTER(C.c_int32), _f32p],
+    "pp2_mdp_qvalues": [_vp, _f32p],
+    "pp2_mdp_control": [_vp, C.c_int, _u8p, _f32p, C.POINTER(C.c_int32)],
     "pp2_fib_reset": [_vp],
     "pp2_fib_sweep": [_vp, C.c_int],
     "pp2_fib_solve": [_vp, C.c_int, _i32p, _f32p],

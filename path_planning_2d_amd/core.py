@@ -261,6 +261,40 @@ class GridContext:
                 raise _lib.Pp2Error(st, "pp2_loop_run", msg.decode() if msg else "")
         return run
 
+    # ------------------------------------------------------------ control
+    CONTROL_MODE = 0   # action of the belief's mode (the reference MDP node)
+    CONTROL_QMDP = 1   # argmin_u of the belief-expected Q over the current J
+    _POLICIES = {"mode": CONTROL_MODE, "qmdp": CONTROL_QMDP}
+
+    def belief_mode(self):
+        """(cell, prob): the first strict maximum > 0 of the normalised belief
+        (cell = y * W + x; (0, 0.0) when no cell is > 0), found on the device."""
+        cell = C.c_int32(0)
+        prob = C.c_float(0.0)
+        call("pp2_belief_mode", self._h, C.byref(cell), C.byref(prob))
+        return cell.value, np.float32(prob.value)
+
+    def mdp_qvalues(self) -> np.ndarray:
+        """q[u] = E_b[C(x, u) + gamma * sum_i T(x, u, i) J(x + off_i)] over the
+        current belief and values (float32[9]), reduced on the device."""
+        q = np.empty(9, np.float32)
+        call("pp2_mdp_qvalues", self._h, _f32(q))
+        return q
+
+    def mdp_control(self, policy="qmdp"):
+        """(action, value, cell) of a control policy: "mode" (or CONTROL_MODE)
+        looks the belief's mode up in the action plane, "qmdp" (CONTROL_QMDP)
+        takes the first minimum of mdp_qvalues() (cell = -1)."""
+        if isinstance(policy, str):
+            if policy not in self._POLICIES:
+                raise ValueError(f"unknown control policy {policy!r}")
+            policy = self._POLICIES[policy]
+        a = C.c_uint8(0)
+        v = C.c_float(0.0)
+        cell = C.c_int32(0)
+        call("pp2_mdp_control", self._h, int(policy), C.byref(a), C.byref(v), C.byref(cell))
+        return a.value, np.float32(v.value), cell.value
+
     # ------------------------------------------------------------ FIB
     def fib_reset(self):
         call("pp2_fib_reset", self._h)

@@ -131,6 +131,12 @@ struct pp2_ctx {
   // false after a pp2_belief_set that breaks that, until the next one
   bool belief_sparse_ok = true;
   bool use_coded = true;           // PP2_TUNE_CODED_MODEL
+  // control selection (pp2_control.cpp), allocated on first use: Q partials
+  // [blocks][9] and mode partials (value, index)[blocks] on the device, and
+  // the pinned record the finalise kernel writes (kControlRec words)
+  float* ctl_buf = nullptr;
+  int ctl_blocks = 0;
+  uint32_t* ctl_host = nullptr;
   void* staging = nullptr;     // dense host-layout staging buffer
   size_t staging_bytes = 0;
 

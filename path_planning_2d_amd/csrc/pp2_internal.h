@@ -231,6 +231,33 @@ hipError_t launch_mdp_sweep_coded(hipStream_t st, const Geom& g, float gamma,
                                   const uint16_t* code, const float* rows, int entries,
                                   bool sparse, const float* J_in, float* J_out, uint8_t* A);
 
+// On-device control selection (pp2_control.hip).  The Q pass writes
+// control_blocks(g) x 9 partials (one row per 1024-cell block of the dense
+// kernels, the same rows from the dense and the coded kernel), the mode pass
+// one (value, index) pair per block; launch_control_finish folds whichever
+// halves are given (nq / nm = 0: none) into the record the host reads (rec may
+// be pinned host memory).
+constexpr int kControlRec = 16;          // 4-byte words: q[0..8], then
+constexpr int kControlRecAction = 9;     //   argmin_u q (first strict minimum)
+constexpr int kControlRecValue = 10;     //   q[argmin]
+constexpr int kControlRecCell = 11;      //   the belief's mode, y * W + x
+constexpr int kControlRecProb = 12;      //   its normalised probability
+constexpr int kControlRecModeAction = 13;  // A and J at the mode
+constexpr int kControlRecModeValue = 14;
+int control_blocks(const Geom& g);
+hipError_t launch_control_q(hipStream_t st, const Geom& g, float gamma, PlaneSet T, PlaneSet C,
+                            const float* J, const float* b, float* partials, bool nt);
+// ncus: CUs of the device (sizes the grid only; 0: a workgroup per tile)
+hipError_t launch_control_q_coded(hipStream_t st, const Geom& g, const uint16_t* code,
+                                  const float* rows, int E, bool sparse, const float* J,
+                                  const float* b, float* partials, int ncus);
+// mass: the divisor of pp2_belief_get (device)
+hipError_t launch_belief_mode(hipStream_t st, const Geom& g, const float* b, const float* mass,
+                              float* pv, int* pi);
+hipError_t launch_control_finish(hipStream_t st, const Geom& g, const float* qpart, int nq,
+                                 const float* mass, const float* pv, const int* pi, int nm,
+                                 const float* J, const uint8_t* A, uint32_t* rec);
+
 // Tile-resident loop (pp2_resident.hip): n fused loop steps of a sparse-coded
 // context in one launch, one tile of rt whole rows per CU kept in LDS,
 // neighbour rows handed over as data-tagged granules, block-start masses

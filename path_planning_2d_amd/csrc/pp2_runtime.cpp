@@ -1686,6 +1686,8 @@ int pp2_destroy(pp2_ctx* c) {
     if (pb) (void)hipFree(pb);
   if (c->rpartials) (void)hipFree(c->rpartials);
   if (c->staging) (void)hipFree(c->staging);
+  if (c->ctl_buf) (void)hipFree(c->ctl_buf);
+  if (c->ctl_host) (void)hipHostFree(c->ctl_host);
   if (c->code_alloc) (void)hipFree(c->code_alloc);
   resident_free(c);
   if (c->res_host) (void)hipHostFree(c->res_host);

@@ -209,6 +209,35 @@ def closed_loop(grid: np.ndarray, b0: np.ndarray, step_fn, max_steps: int,
             np.array(vals, np.float32))
 
 
+def control_reference(T, C, J, b, gamma, H, W):
+    """Reference of the control selection (pp2_mdp_qvalues / pp2_belief_mode):
+    (q64[9], mode_cell).  Q[x, u] = C[x, u] + sum_i fl32(gamma * T[x, u, i]) *
+    J(x + off_i) in fp64 from the fp32 products gamma * T (what the sweep
+    multiplies J by), J = 0 outside the grid; q = b @ Q / sum(b) in fp64.  The
+    mode is the first strict maximum > 0 of the float32 belief (cell 0 when
+    there is none).  A batch of beliefs b[m, hw] gives (q64[m, 9], cells[m])."""
+    n = H * W
+    gT = (np.float32(gamma) * np.asarray(T, np.float32).reshape(n, 9, 9)).astype(np.float32)
+    Jp = np.zeros((H + 2, W + 2), np.float64)
+    Jp[1:-1, 1:-1] = np.asarray(J, np.float32).reshape(H, W)
+    Q = np.asarray(C, np.float32).reshape(n, 9).astype(np.float64)
+    for i in range(9):
+        oy, ox = i // 3, i % 3
+        Q += gT[:, :, i].astype(np.float64) * Jp[oy:oy + H, ox:ox + W].reshape(n, 1)
+    b32 = np.asarray(b, np.float32)
+    single = b32.ndim == 1
+    b32 = b32.reshape(-1, n)
+    b64 = b32.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = b64 @ Q / b64.sum(axis=1, keepdims=True)
+    # argmax returns the first maximum; NaNs and values <= 0 never win
+    cand = np.where(b32 > 0, b32, np.float32(0.0))
+    cells = np.where(cand.max(axis=1) > 0, cand.argmax(axis=1), 0).astype(np.int64)
+    if single:
+        return q[0], int(cells[0])
+    return q, cells
+
+
 def action_parity(acts_a, vals_a, acts_b, vals_b) -> dict:
     """Plan-step parity of two closed loops over their common steps: the
     actions equal and the values equal as fp32 bit patterns, step by step
