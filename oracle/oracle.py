@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(HERE, "libpp2_oracle.so")
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
+_u16p = np.ctypeslib.ndpointer(np.uint16, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 
@@ -49,6 +50,7 @@ def lib():
             "orc_model_mdp": (None, [I, I, _u8p, I, I, _f32p, _f32p]),
             "orc_belief_update": (None, [I, I, _f32p, _f32p, _f32p, I, I, _f32p, I]),
             "orc_belief_update_rows": (None, [I, I, _f32p, _f32p, _f32p, I, I, _f32p, I, I, I]),
+            "orc_rollout_step_f16": (D, [I, I, _f32p, _f32p, _f32p, I, I, _u16p, F, _f32p]),
             "orc_normalize_seq": (F, [S, _f32p]),
             "orc_normalize_f64": (D, [S, _f32p]),
             "orc_sum_seq": (F, [S, _f32p]),
@@ -143,6 +145,52 @@ def belief_step(H, W, T, L, b, u, z, mode="seq"):
     (search_tree_cuda.cu:601-612)."""
     out = belief_update(H, W, T, L, b, u, z)
     return normalize_seq(out)[0] if mode == "seq" else normalize_f64(out)[0]
+
+
+# ---------------------------------------------------------------- fp16 rollout
+def rollout_step_f16(H, W, T, L, R, u, z, plane, max_in):
+    """One step of the batched fp16 rollout (k_rollout_band) restated exactly
+    (orc_rollout_step_f16).  ``plane``: the stored input plane, fp16 [H*W];
+    ``max_in``: its stored max.  Returns (out, v, stats): the stored output
+    plane fp16(v) (round to nearest even, fp16 subnormals kept), the unrounded
+    fp32 v, and the step's statistics in float64 as pp2_rollout_results uses
+    them: (sum of out, max of out, <plane, R[:,u]>)."""
+    plane = np.ascontiguousarray(plane, np.float16).reshape(H * W)
+    v = np.empty(H * W, np.float32)
+    rdot = lib().orc_rollout_step_f16(H, W, T, L, R, int(u), int(z), plane.view(np.uint16),
+                                      float(np.float32(max_in)), v)
+    out = v.astype(np.float16)
+    o64 = out.astype(np.float64)
+    return out, v, (float(o64.sum()), float(o64.max()), float(rdot))
+
+
+def rollout_root_f16(b0):
+    """pp2_rollout_set_root's image: fp16(b / max(b)), the division in fp32."""
+    b0 = np.ascontiguousarray(b0, np.float32).reshape(-1)
+    return (b0 / b0.max()).astype(np.float16)
+
+
+def rollout_chain_f16(H, W, T, L, R, b0, us, zs):
+    """The depth steps of one copy chained from the root image, every stored
+    plane bit-exact.  ``us``, ``zs``: the copy's [depth] actions and
+    observations.  Returns a dict: ``rewards`` and ``obs_prob`` [depth] in
+    float64 by the host formulas of pp2_rollout_results on the planes' float64
+    statistics (<B_k, R_u> / S_k and S_{k+1} M_k / S_k), ``planes`` (the stored
+    fp16 plane after every step), ``plane`` (the last of them) and ``belief``,
+    exactly as pp2_rollout_get_belief forms it: float32(float64(h) / sum)."""
+    h = rollout_root_f16(b0)
+    h64 = h.astype(np.float64)
+    s, m = float(h64.sum()), float(h64.max())
+    rw, pr, planes = [], [], []
+    for u, z in zip(us, zs):
+        h, _, (s1, m1, rd) = rollout_step_f16(H, W, T, L, R, u, z, h, m)
+        rw.append(rd / s)
+        pr.append(s1 * m / s)
+        s, m = s1, m1
+        planes.append(h)
+    h64 = h.astype(np.float64)
+    return {"rewards": np.array(rw), "obs_prob": np.array(pr), "planes": planes, "plane": h,
+            "belief": (h64 / h64.sum()).astype(np.float32)}
 
 
 # ---------------------------------------------------------------- MDP

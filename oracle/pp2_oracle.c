@@ -180,6 +180,45 @@ void orc_belief_update(int H, int W, const float* T, const float* L,
   orc_belief_update_rows(H, W, T, L, b_in, u, z, b_out, ftz, 0, H);
 }
 
+/* ---- batched fp16 rollout step --------------------------------------------- */
+/* fp16 bit pattern -> float, exact (subnormals are values, not flushed) */
+static float half_bits_to_float(uint16_t h) {
+  const int e = (h >> 10) & 0x1f, m = h & 0x3ff;
+  float v;
+  if (e == 0) v = ldexpf((float)m, -24);
+  else if (e == 31) v = m ? NAN : INFINITY;
+  else v = ldexpf((float)(m | 0x400), e - 25);
+  return (h & 0x8000) ? -v : v;
+}
+
+double orc_rollout_step_f16(int H, int W, const float* T, const float* L,
+                            const float* R, int u, int z, const uint16_t* b_in,
+                            float max_in, float* v_out) {
+  const float inv = 1.0f / max_in;
+  double rdot = 0.0;
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t idx = (size_t)y * W + x;
+      const float li = ftzf(L[16 * idx + z] * inv, 1);
+      float p = 0.0f;
+      int s = 0;
+      for (int oy = -1; oy < 2; ++oy)
+        for (int ox = -1; ox < 2; ++ox, ++s) {
+          const int sx = x + ox, sy = y + oy;
+          float t = 0.0f, b = 0.0f;
+          if (sx >= 0 && sx < W && sy >= 0 && sy < H) {
+            const size_t sidx = (size_t)sy * W + sx;
+            t = ftzf(T[81 * sidx + 9 * u + (8 - s)], 1);
+            b = half_bits_to_float(b_in[sidx]);
+          }
+          p = ftzf(fmaf(t, b, p), 1);
+        }
+      v_out[idx] = ftzf(p * li, 1);
+      rdot += (double)half_bits_to_float(b_in[idx]) * (double)R[9 * idx + u];
+    }
+  return rdot;
+}
+
 float orc_sum_seq(size_t n, const float* b) {
   float s = 0.0f;
   for (size_t i = 0; i < n; ++i) s = s + b[i];

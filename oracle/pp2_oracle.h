@@ -63,6 +63,21 @@ double orc_normalize_f64(size_t n, float* b);
 double orc_sum_f64(size_t n, const float* b);
 float orc_sum_seq(size_t n, const float* b);
 
+/* ---- one step of the batched fp16 rollout (k_rollout_band), restated exactly -
+ * b_in: the stored input plane [H][W] as fp16 bit patterns (subnormals are
+ * values); max_in: its stored max.  Per cell, in fp32 with libm fmaf:
+ *   inv = 1.0f / max_in;  li = L[x][z] * inv;
+ *   p = 0;  for s = 0..8 ascending: p = fmaf(T[x+off_s][u][8-s], b[x+off_s], p)
+ *           (the term is fmaf(0, 0, p) outside the grid);
+ *   v = p * li;
+ * fp32 subnormal operands and results flush to zero (the device build's FTZ).
+ * v_out [H][W] gets the unrounded v; the stored plane is fp16(v), round to
+ * nearest even with fp16 subnormals kept (oracle.py rounds in numpy).
+ * Returns the step's reward statistic <b_in, R[:,u]> in float64. */
+double orc_rollout_step_f16(int H, int W, const float* T, const float* L,
+                            const float* R, int u, int z, const uint16_t* b_in,
+                            float max_in, float* v_out);
+
 /* ---- MDP Bellman backup (a4) ---------------------------------------------- */
 /* cudaOneStepValueIteration: src/mdp/path_planning_2d_cuda.cu:215-264 */
 void orc_mdp_sweep(int H, int W, float gamma, const float* T, const float* C,

@@ -32,7 +32,12 @@
 //    copy by k_rollout_reduce (pp2_kernels.hip) in a fixed order.
 // Per cell the arithmetic is the dense update's: p = sum_s fmaf(T, b, p) in
 // ascending stencil order s, then p * fl(L_z / max).  The coded and dense
-// model sources give bit-identical beliefs and statistics.
+// model sources give bit-identical beliefs and statistics.  Stored fp16
+// subnormals are values, in the next step's input and in every statistic
+// (the build's FTZ covers fp32 only; v_fma_mix_f32, v_dot2c_f32_f16 and
+// v_cvt_pk_f16_f32 keep fp16 subnormals on gfx950).  The stored planes are
+// held bit for bit to orc_rollout_step_f16 (oracle/pp2_oracle.c), which
+// restates this chain: tests/test_gpu_rollout_exact.py.
 
 #include <type_traits>
 
