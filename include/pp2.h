@@ -508,6 +508,82 @@ int pp2_rollout_results(pp2_rollout* r, float* rewards, float* obs_prob,
  * run (hw floats) */
 int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
 
+/* ---------------------------------------------------------------- episodes
+ * Batched closed-loop policy episodes (what the reference does by running its
+ * node against dummy_simulator): E simulated robots, each with its own fp32
+ * belief, follow a control policy for up to `horizon` steps in one launch --
+ * one workgroup per episode, the belief in LDS.  Needs an unsharded context
+ * with a model, current J and A, and an active dictionary-coded model with
+ * factored rows (pp2_model_dict_info), whose belief fits the LDS of one
+ * workgroup (100x40 and 97x131 do, 256x256 does not: PP2_EINVAL).
+ *
+ * Episode e: true cell s = start_cells[e] (y*W + x), stored belief b = b0,
+ * cost G = +0, discount d = 1.  If s is the goal: steps 0, status 1, belief
+ * b0.  Else each step k = 0 .. horizon-1:
+ *  1. control.  PP2_CONTROL_MODE: cell = the smallest y*W + x whose stored
+ *     b > 0 and is >= every other cell (cell 0 if none; NaNs never win),
+ *     u = A[cell].  The stored values are compared -- the belief is only ever
+ *     rescaled by powers of two -- so ties can break differently from
+ *     pp2_belief_mode, which compares the quotients b / mass.
+ *     PP2_CONTROL_QMDP: S_u = sum_i b[i] Q_u[i] in the pinned order below,
+ *     u = the first strict minimum over u = 0..8 from FLT_MAX (no division by
+ *     the mass: the argmin does not need it).
+ *  2. cost.  G = G + fl(d * C[s][u]), then d = fl(d * gamma): C the MDP cost
+ *     of pp2_model_download, separate roundings (no fmaf).
+ *  3. motion.  r = U(e, 2k); c = +0, then for i = 0..8 c = c + T[s][u][i]
+ *     (fp32): the first i with T[s][u][i] > 0 and r < c, else i = 4; s moves
+ *     by (i%3 - 1, i/3 - 1) (a move off the grid, which no generated model
+ *     allows, is not taken).
+ *  4. observation.  r = U(e, 2k+1); the same scan over L[s'][0..15], else 15.
+ *  5. belief.  raw = pp2_belief_update's unnormalised update of the stored b
+ *     by (u, z) (the fmaf chain, then * L_z, flush-to-zero); m = max(raw).
+ *     If m is not a finite value > 0: status 2 (belief lost), steps k+1, the
+ *     stored belief is raw, stop.  Else e2 = clamp(exponent(m), -126, 126) and
+ *     the stored belief is raw * 2^-e2 (exact, flush-to-zero): max in [1, 2).
+ *  6. goal.  s' = goal: status 1, steps k+1, stop.  Still running after the
+ *     last step: status 0, steps = horizon.
+ * Random numbers are counter based: mix = splitmix64's finaliser, Gm =
+ * 0x9E3779B97F4A7C15, key_e = mix(seed + Gm*(e+1)), x = mix(key_e + Gm*(d+1)),
+ * U(e, d) = float(x >> 40) * 2^-24 (mod 2^64).  An episode depends on
+ * (seed, e) only: not on E, the workgroup count or earlier runs.
+ * Q planes: once per run from the current J, Q_u[x] = pp2_mdp_sweep's cost of
+ * action u (C, then nine fmaf(fl(gamma T_i), J_i, .) in i order, J = 0 off
+ * the grid), stored as [u][row][row stride] with pad cells +0.
+ * Pinned Q-dot order, over the padded index i = y*stride + x, NP = H*stride
+ * (pads add +0): 256 lanes; lane t from +0, for j = 0, 1, .. and k = 0..3 with
+ * i = 1024j + 4t + k < NP: acc = acc + fl(b[i] * Q_u[i]); each group of 64
+ * lanes folded by the xor butterfly 32, 16, 8, 4, 2, 1; then
+ * ((w0 + w1) + w2) + w3. */
+typedef struct pp2_episodes pp2_episodes;
+/* episodes 1..131072, horizon 1..4096; record_trace != 0 keeps the per-step
+ * trace.  PP2_ESTATE: no model, a row shard or group member, coded model
+ * inactive or not factored.  PP2_EINVAL: the grid does not fit LDS. */
+int pp2_episodes_create(pp2_episodes** out, pp2_ctx* ctx, int episodes, int horizon,
+                        int record_trace);
+int pp2_episodes_destroy(pp2_episodes* ep);
+/* b0: hw floats, every entry finite and >= +0; start_cells: [episodes] in
+ * [0, hw) (else PP2_EINVAL).  Settles pending work of the context first and
+ * re-checks its model, then reads the current J and A.  Asynchronous. */
+int pp2_episodes_run(pp2_episodes* ep, int policy, uint64_t seed, const float* b0,
+                     const int32_t* start_cells);
+/* [episodes] each, any may be NULL: steps taken, status (0 horizon reached,
+ * 1 goal reached, 2 belief lost), discounted cost G, the last true cell.
+ * Synchronises. */
+int pp2_episodes_results(pp2_episodes* ep, int32_t* steps, uint8_t* status, float* cost,
+                         int32_t* final_cell);
+/* The last run's trace, [horizon][episodes] (qsums [horizon][episodes][9]),
+ * any may be NULL: action, observation, true cell after the move, the S_u
+ * (PP2_CONTROL_QMDP runs only), the mode cell (PP2_CONTROL_MODE runs only).
+ * Steps not taken hold 255, 255, -1, 0, -1.  PP2_ESTATE without record_trace. */
+int pp2_episodes_trace(pp2_episodes* ep, uint8_t* actions, uint8_t* observations,
+                       int32_t* cells, float* qsums, int32_t* mode_cells);
+/* the stored belief of one episode after the run (hw floats) */
+int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief);
+/* the Q planes of the last run as Q[hw][9] */
+int pp2_episodes_get_q(pp2_episodes* ep, float* Q);
+/* LDS bytes per workgroup, workgroups and threads per workgroup of a launch */
+int pp2_episodes_info(pp2_episodes* ep, int* lds_bytes, int* workgroups, int* threads);
+
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):
  *  - one process per GPU: RCCL (pp2_rccl_unique_id / pp2_shard_comm_init);

@@ -1,0 +1,102 @@
+// pp2_episodes.h -- private: batched closed-loop policy episodes
+// (pp2_episodes.hip kernels, pp2_episodes.cpp C ABI; include/pp2.h "episodes").
+//
+// One 256-thread workgroup keeps one episode's belief in LDS (two planes,
+// ping-pong, with zero halo rows and zero x pads) and runs the whole horizon in
+// one launch: control, motion, observation, belief update, rescale.  The
+// dynamic LDS of a workgroup, in floats from its start:
+//   ct     CT of the factored sweep rows ([9][kFactK] x 4 floats, C_a at .x):
+//          the step cost C[s][u]
+//   rf     the class tables (QR raw T quads, LT L columns: kResTab floats),
+//          then the LX bytes of the E entries
+//   cls    [9][pad4(E)] bytes: 4 * (class of entry e for action u), the float
+//          offset of its quad in QR / CT -- the IW records transposed, so that
+//          a step's gathers index one dense E-byte table (a 16-B IW record
+//          per entry puts every read on 16 of the 64 banks)
+//   code   the code plane, uint16 [H + 2][ps] (off-grid cells and pads: 0)
+//   red    reduction scratch (kEpRedFloats)
+//   b[2]   the belief planes, fp32 [H + 2][ps] + 4
+// with ps = wp + 4: cell (y, x) of a plane sits at (y + 1) * ps + 4 + x, so
+// x = -1 is the row's last left pad and x = wp the next row's first.
+#pragma once
+#include "pp2_internal.h"
+
+namespace pp2 {
+
+constexpr int kEpThreads = 256;
+constexpr int kEpRedFloats = 48;
+constexpr int kEpMaxPerCu = 8;  // workgroups per CU the grid is sized for
+
+struct EpisodeLds {
+  int ps, prows;                         // plane row stride (floats), plane rows
+  int epad;                              // bytes per action of cls
+  int ct, rf, cls, code, red, b0, b1;    // offsets in floats
+  int total;                             // floats
+};
+constexpr int kEpCtFloats = 9 * kFactK * 4;
+__host__ __device__ inline int ep_pad4(int n) { return (n + 3) & ~3; }
+// floats of the tables in front of the code plane
+__host__ __device__ inline int ep_table_floats(int E) {
+  return kEpCtFloats + ep_pad4(kResTab + ((E + 3) >> 2)) + ep_pad4(9 * (ep_pad4(E) >> 2));
+}
+__host__ __device__ inline EpisodeLds episode_lds(const Geom& g, int E) {
+  EpisodeLds l;
+  l.ps = g.wp + 4;
+  l.prows = g.rows + 2;
+  l.epad = ep_pad4(E);
+  const int plane = l.prows * l.ps + 4;
+  const int codef = ep_pad4((l.prows * l.ps + 8) >> 1);
+  l.ct = 0;
+  l.rf = l.ct + kEpCtFloats;
+  l.cls = l.rf + ep_pad4(kResTab + ((E + 3) >> 2));
+  l.code = ep_table_floats(E);
+  l.red = l.code + codef;
+  l.b0 = l.red + kEpRedFloats;
+  l.b1 = l.b0 + plane;
+  l.total = l.b1 + plane;
+  return l;
+}
+// LDS bytes of one workgroup; a batch is admitted only if this is at most
+// kDictLdsMaxBytes (64-bit: the planes of a large grid overflow int floats).
+inline long long episode_lds_bytes(const Geom& g, int E) {
+  const long long ps = g.wp + 4, prows = (long long)g.rows + 2;
+  const long long plane = prows * ps + 4;
+  const long long codef = (((prows * ps + 8) >> 1) + 3) & ~3LL;
+  return 4 * (ep_table_floats(E) + codef + kEpRedFloats + 2 * plane);
+}
+
+struct EpisodeRun {
+  Geom g;
+  int E;                     // dictionary entries
+  const uint16_t* code;      // code plane (row 0, x 0)
+  const float* rows;         // factored sweep rows
+  const float* rfact;        // class tables, then the LX bytes
+  const float* Q;            // [9][H][wp], pads +0
+  const uint8_t* A;          // [H][wp]
+  const float* b0;           // [H][wp], pads +0
+  const int32_t* start;      // [episodes], y * W + x
+  int episodes, horizon;
+  unsigned long long seed;
+  float gamma;
+  int goal;                  // y * W + x
+  int32_t* steps;            // [episodes]
+  uint8_t* status;
+  float* cost;
+  int32_t* final_cell;
+  float* beliefs;            // [episodes][H][wp]
+  // trace, [horizon][episodes] (null: not recorded)
+  uint8_t* tr_u;
+  uint8_t* tr_z;
+  int32_t* tr_cell;
+  float* tr_q;               // [horizon][episodes][9]
+  int32_t* tr_mode;
+};
+
+// Q[u][y][x] = k_mdp_sweep's cost of action u from J (sparse coded model).
+hipError_t launch_episode_qplanes(hipStream_t st, const Geom& g, const uint16_t* code,
+                                  const float* rows, int E, const float* J, float* Q, int ncus);
+// policy: PP2_CONTROL_MODE (0) or PP2_CONTROL_QMDP (1).  hipErrorInvalidValue
+// when the workgroup's LDS does not fit.
+hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups);
+
+}  // namespace pp2

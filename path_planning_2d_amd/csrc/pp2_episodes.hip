@@ -1,0 +1,446 @@
+// pp2_episodes.hip -- batched closed-loop policy episodes on the device
+// (gfx950): k_episode_qplanes writes the nine Q planes of the current J, and
+// k_episodes runs E independent episodes -- select a control from the belief,
+// move the true robot, sample the observation, update the belief -- each
+// wholly inside one workgroup whose LDS holds the episode's belief
+// (pp2_episodes.h has the LDS layout, include/pp2.h "episodes" the semantics).
+//
+// Every quantity is a function of (seed, episode) and the geometry alone:
+//  * lane t of the 256 owns the padded plane indices i = 1024 j + 4 t + k
+//    (k = 0..3, i < H * wp) for the control reduction, the stencil and the
+//    max, so a cell is only ever written by its own lane; the rescale by
+//    2^-e2 is not a pass of its own: the plane keeps the raw update and every
+//    read multiplies by the step's power of two (exact, the same bits);
+//  * the Q dot is acc = acc + fl(b * Q) per lane in ascending i (separate
+//    roundings: the file is built with -ffp-contract=off), wave_sum's xor
+//    butterfly per wave, then ((w0 + w1) + w2) + w3;
+//  * the mode is a (value, index) maximum under a total order, and the belief
+//    maximum a plain max: both are exact in any order;
+//  * the sampling (counter-based splitmix64 draws, the cumulative scans of the
+//    true cell's T row and L row from the class tables) is computed by every
+//    lane redundantly from workgroup-uniform values, so a step needs two
+//    barriers and no broadcast.
+// The belief update is belief_vals' arithmetic (the fmaf chain over the
+// action's support in ascending s, then * L_z), gathered by class: raw T of a
+// source cell = QR[u][class of its entry for u], L_z = LT[z][L class].
+// Off-grid window cells hold b = +0 and code 0, whose finite T adds nothing.
+// No atomics, no waits between workgroups, every loop bounded.
+#include <limits.h>
+
+#include "pp2_coded_dev.h"
+#include "pp2_episodes.h"
+
+namespace pp2 {
+namespace {
+
+constexpr int kQ = 9;
+
+// support cells of the actions (kSup / kSupN), indexed at run time
+__constant__ unsigned char cSupN[9] = {4, 4, 4, 4, 1, 4, 4, 4, 4};
+__constant__ unsigned char cSup[9][4] = {{0, 1, 3, 4}, {0, 1, 2, 4}, {1, 2, 4, 5},
+                                         {0, 3, 4, 6}, {4, 0, 0, 0}, {2, 4, 5, 8},
+                                         {3, 4, 6, 7}, {4, 6, 7, 8}, {4, 5, 7, 8}};
+
+// ---- Q planes ---------------------------------------------------------------
+// k_control_q_coded's structure without the belief: the nine costs of a cell
+// (sweep_cell_fact's fmaf chains) stored instead of folded.
+__global__ __launch_bounds__(kBlock) void k_episode_qplanes(
+    Geom g, const uint16_t* __restrict__ code, const float* __restrict__ rows, int E,
+    const float* __restrict__ J, int nblocks, float* __restrict__ Q) {
+  extern __shared__ float lds[];
+  const int tpr = g.wp / 4;
+  const long long np = (long long)g.rows * g.wp;
+  stage_rows(rows, rows_floats(E, true), lds);
+  __syncthreads();
+  const char* qt = reinterpret_cast<const char*>(lds + kFactQT);
+  const char* ct = reinterpret_cast<const char*>(lds + kFactCT);
+  for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const long long t = (long long)blk * kBlock + threadIdx.x;
+    const int y = (int)(t / tpr);
+    const int x0 = (int)(t % tpr) * 4;
+    if (y >= g.rows) continue;
+    const long long off = (long long)y * g.wp + x0;
+    const uint2 m = *reinterpret_cast<const uint2*>(code + off);
+    const uint32_t cc[4] = {m.x & 0xffffu, m.x >> 16, m.y & 0xffffu, m.y >> 16};
+    float jn[9][4];
+    load_jn(J, g.wp, y, x0, x0 == 0, x0 + 4 == g.wp, jn);
+    float q[kQ][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 iw = *reinterpret_cast<const uint4*>(lds + kFactIW + 4 * cc[k]);
+#pragma unroll
+      for (int a = 0; a < kQ; ++a) {
+        const uint32_t w = a < 4 ? iw.x : a < 8 ? iw.y : iw.z;
+        const uint32_t o = __builtin_amdgcn_ubfe(w, 8 * (a % 4), 8);
+        const int tab = a * kFactK * 16;
+        float tv[4];
+        if (kSupN[a] == 1) {
+          tv[0] = *reinterpret_cast<const float*>(qt + tab + o);
+        } else {
+          const f4a tq = *reinterpret_cast<const f4a*>(qt + tab + o);
+          tv[0] = tq[0]; tv[1] = tq[1]; tv[2] = tq[2]; tv[3] = tq[3];
+        }
+        float cost = *reinterpret_cast<const float*>(ct + tab + o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < kSupN[a]) cost = __builtin_fmaf(tv[j], jn[kSup[a][j]][k], cost);
+        q[a][k] = x0 + k < g.width ? cost : 0.0f;  // pad cells: +0
+      }
+      __builtin_amdgcn_sched_barrier(0);  // one cell's table reads live at a time
+    }
+#pragma unroll
+    for (int a = 0; a < kQ; ++a) store4<false>(Q + a * np + off, q[a]);
+  }
+}
+
+// ---- random numbers ---------------------------------------------------------
+constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// U(e, d) of the episode with key key_e: 24 bits, [0, 1)
+__device__ __forceinline__ float draw(unsigned long long key, unsigned d) {
+  const unsigned long long x = mix64(key + kGolden * (unsigned long long)(d + 1u));
+  return (float)(unsigned)(x >> 40) * 5.9604644775390625e-08f;  // 2^-24, exact
+}
+
+// ---- belief gather of one quad ----------------------------------------------
+// cw: the codes of the window (rows y-1 .. y+1, x0-1 .. x0+4), win: its
+// beliefs.  p[k] = sum over the support of U, ascending s, of
+// T[x + off_s][U][8 - s] * b(x + off_s) (belief_vals' chain).
+// cu: the class bytes of action U (4 * class per entry), qr: its QR table.
+template <int U>
+__device__ __forceinline__ void ep_gather(const uint8_t* cu, const float* qr,
+                                          const uint32_t (&cw)[3][6], const float (&win)[3][6],
+                                          float (&p)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k] = 0.0f;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int sl = sup_slot(U, 8 - s);
+    if (sl < 0) continue;
+    const int wr = s / 3, wc = s % 3 - 1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      p[k] = __builtin_fmaf(qr[cu[cw[wr][k + 1 + wc]] + sl], win[wr][k + 1 + wc], p[k]);
+  }
+}
+__device__ __forceinline__ void ep_gather_any(int u, const uint8_t* cu, const float* qr,
+                                              const uint32_t (&cw)[3][6],
+                                              const float (&win)[3][6], float (&p)[4]) {
+  switch (u) {
+#define PP2_EG(UU) \
+  case UU: ep_gather<UU>(cu, qr, cw, win, p); break;
+    PP2_EG(0) PP2_EG(1) PP2_EG(2) PP2_EG(3) PP2_EG(4) PP2_EG(5) PP2_EG(6) PP2_EG(7)
+    default: ep_gather<8>(cu, qr, cw, win, p);
+#undef PP2_EG
+  }
+}
+
+__device__ __forceinline__ void mode_take(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+// ---- the episodes -----------------------------------------------------------
+// The lane's quads in ascending padded index I0 = 4 tid + 1024 j < NP, with
+// their row Y and first column X0 stepped instead of divided out (a quad
+// never straddles a row: wp is a multiple of 4).
+#define PP2_EP_QUADS(I0, Y, X0)                                                   \
+  for (int I0 = 4 * tid, Y = qy0, X0 = qx0; I0 < NP; I0 += 4 * kEpThreads, Y += qdy, \
+           X0 += qdx, Y += X0 >= wp ? 1 : 0, X0 -= X0 >= wp ? wp : 0)
+
+template <int POLICY>
+__global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Geom g = a.g;
+  const EpisodeLds L = episode_lds(g, a.E);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int H = g.rows, W = g.width, wp = g.wp, ps = L.ps;
+  const int NP = H * wp;
+  const int planef = L.prows * ps + 4;
+  const int qy0 = 4 * tid / wp, qx0 = 4 * tid - qy0 * wp;          // PP2_EP_QUADS
+  const int qdy = 4 * kEpThreads / wp, qdx = 4 * kEpThreads - qdy * wp;
+  float* sCT = lds + L.ct;
+  float* sRf = lds + L.rf;
+  uint8_t* sCls = reinterpret_cast<uint8_t*>(lds + L.cls);
+  uint16_t* sCode = reinterpret_cast<uint16_t*>(lds + L.code);
+  float* red = lds + L.red;  // [4][9] Q partials | 36: mode v[4] | 40: mode i[4] | 44: max[4]
+  int* redi = reinterpret_cast<int*>(red);
+  const uint8_t* sLX = reinterpret_cast<const uint8_t*>(sRf + kResLX);
+  const float* sLT = sRf + kResLT;
+  const float* sQR = sRf + kResQR;
+
+  // once per workgroup: the tables and the code plane
+  // (plain copies: once per persistent workgroup, and no LDS-DMA slack to pay
+  // for in every workgroup's LDS)
+  for (int i = tid; i < kEpCtFloats; i += kEpThreads) sCT[i] = a.rows[kFactCT + i];
+  for (int i = tid; i < kResTab + ((a.E + 3) >> 2); i += kEpThreads) sRf[i] = a.rfact[i];
+  {
+    const uint32_t* iw = reinterpret_cast<const uint32_t*>(a.rows + kFactIW);
+    for (int i = tid; i < kQ * L.epad; i += kEpThreads) {
+      const int q = i / L.epad, en = i - q * L.epad;
+      uint32_t cb = 0;  // 16 * class -> 4 * class, the float offset of the class's quad
+      if (en < a.E) cb = ((iw[4 * en + (q >> 2)] >> (8 * (q & 3))) & 0xffu) >> 2;
+      sCls[i] = (uint8_t)cb;
+    }
+  }
+  const int ncode = L.prows * ps + 8;
+  for (int i = tid; i < ncode; i += kEpThreads) {
+    const int r = i / ps, c = i - r * ps;
+    const int y = r - 1, x = c - 4;
+    uint16_t v = 0;
+    if (r < L.prows && y >= 0 && y < H && x >= 0 && x < W) v = a.code[(long long)y * wp + x];
+    sCode[i] = v;
+  }
+
+  for (int e = blockIdx.x; e < a.episodes; e += gridDim.x) {
+    __syncthreads();  // the previous episode's planes are no longer read
+    float* cur = lds + L.b0;
+    float* nxt = lds + L.b1;
+    for (int i = tid; i < planef; i += kEpThreads) {
+      const int r = i / ps, c = i - r * ps;
+      const int y = r - 1, x = c - 4;
+      float v = 0.0f;
+      if (r < L.prows && y >= 0 && y < H && x >= 0 && x < wp) v = a.b0[(long long)y * wp + x];
+      cur[i] = v;
+      nxt[i] = 0.0f;
+    }
+    __syncthreads();
+
+    const unsigned long long key = mix64(a.seed + kGolden * (unsigned long long)(e + 1));
+    const int s0 = a.start[e];
+    int sx = s0 % W, sy = s0 / W;
+    float G = 0.0f, disc = 1.0f;
+    // The plane holds the last raw update; the stored belief is plane * sc,
+    // sc = 2^-e2 of that update, an exact multiply (flush-to-zero) applied
+    // wherever the plane is read -- the same bits as a rescaled plane, without
+    // a pass over it.
+    float sc = 1.0f;
+    int steps = a.horizon, status = 0;
+    if (s0 == a.goal) { steps = 0; status = 1; }
+
+    for (int k = 0; k < a.horizon && status == 0; ++k) {
+      // 1. control: the lane's partials
+      int u = 0, mcell = 0;
+      if constexpr (POLICY == 1) {
+        float acc[kQ];
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) acc[q] = 0.0f;
+        PP2_EP_QUADS(i0, y, x0) {
+          const f4a bv = *reinterpret_cast<const f4a*>(cur + (y + 1) * ps + 4 + x0);
+#pragma unroll
+          for (int q = 0; q < kQ; ++q) {
+            const f4a qv = *reinterpret_cast<const f4a*>(a.Q + (long long)q * NP + i0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float bs = bv[j] * sc;
+              const float pr = bs * qv[j];
+              acc[q] = acc[q] + pr;
+            }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+          const float v = wave_sum(acc[q]);
+          if (lane == 0) red[wave * kQ + q] = v;
+        }
+      } else {
+        float v = 0.0f;
+        int idx = INT_MAX;
+        PP2_EP_QUADS(i0, y, x0) {
+          const f4a bv = *reinterpret_cast<const f4a*>(cur + (y + 1) * ps + 4 + x0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+          {
+            const float bs = bv[j] * sc;
+            if (x0 + j < W && bs > v) { v = bs; idx = y * W + x0 + j; }
+          }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+          const float ov = __shfl_xor(v, o);
+          const int oi = __shfl_xor(idx, o);
+          mode_take(v, idx, ov, oi);
+        }
+        if (lane == 0) { red[36 + wave] = v; redi[40 + wave] = idx; }
+      }
+      __syncthreads();
+      if constexpr (POLICY == 1) {
+        float best = FLT_MAX;
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+          const float sq = ((red[q] + red[kQ + q]) + red[2 * kQ + q]) + red[3 * kQ + q];
+          if (sq < best) { best = sq; u = q; }
+          if (a.tr_q && tid == q) a.tr_q[((long long)k * a.episodes + e) * kQ + q] = sq;
+        }
+      } else {
+        float v = red[36];
+        int idx = redi[40];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) mode_take(v, idx, red[36 + j], redi[40 + j]);
+        mcell = idx == INT_MAX ? 0 : idx;
+        u = a.A[(long long)(mcell / W) * wp + mcell % W];
+        if (u > 8) u = 8;  // (an action plane never holds more; keeps the tables' bounds)
+      }
+      u = __builtin_amdgcn_readfirstlane(u);
+
+      // 2. cost, 3. motion, 4. observation: every lane, from uniform values
+      {
+        const uint32_t cs = sCode[(sy + 1) * ps + 4 + sx];
+        const uint32_t cls = sCls[u * L.epad + cs];  // 4 * class
+        const float cv = sCT[u * kFactK * 4 + cls];
+        const float dc = disc * cv;
+        G = G + dc;
+        disc = disc * a.gamma;
+        const float r = draw(key, 2u * (unsigned)k);
+        const float* tq = sQR + u * kFactK * 4 + cls;
+        float c = 0.0f;
+        int mv = 4;
+        bool found = false;
+        const int n = cSupN[u];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < n) {
+            const float t = tq[j];
+            c = c + t;
+            if (!found && t > 0.0f && r < c) { found = true; mv = cSup[u][j]; }
+          }
+        }
+        const int nx = sx + mv % 3 - 1, ny = sy + mv / 3 - 1;
+        // (a move off the grid is not taken: no generated model has one)
+        if (nx >= 0 && nx < W && ny >= 0 && ny < H) { sx = nx; sy = ny; }
+      }
+      int z = 15;
+      {
+        const float r = draw(key, 2u * (unsigned)k + 1u);
+        const uint32_t lx = sLX[sCode[(sy + 1) * ps + 4 + sx]] >> 2;
+        float c = 0.0f;
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float l = sLT[i * kResLK + lx];
+          c = c + l;
+          if (!found && l > 0.0f && r < c) { found = true; z = i; }
+        }
+      }
+      z = __builtin_amdgcn_readfirstlane(z);
+      if (a.tr_u && tid == 0) {
+        const long long at = (long long)k * a.episodes + e;
+        a.tr_u[at] = (uint8_t)u;
+        a.tr_z[at] = (uint8_t)z;
+        a.tr_cell[at] = sy * W + sx;
+        if (POLICY == 0) a.tr_mode[at] = mcell;
+      }
+
+      // 5. belief: raw update of the lane's quads, and their maximum
+      float m = 0.0f;
+      const float* lt = sLT + z * kResLK;
+      const uint8_t* cu = sCls + u * L.epad;
+      const float* qru = sQR + u * kFactK * 4;
+      // (two quads' LDS chains -- codes, class bytes, T -- in flight together)
+#pragma unroll 2
+      PP2_EP_QUADS(i0, y, x0) {
+        float win[3][6];
+        uint32_t cw[3][6];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const int at = (y + r) * ps + 4 + x0;
+          const f4a mid = *reinterpret_cast<const f4a*>(cur + at);
+          win[r][0] = cur[at - 1] * sc;
+          win[r][1] = mid[0] * sc; win[r][2] = mid[1] * sc;
+          win[r][3] = mid[2] * sc; win[r][4] = mid[3] * sc;
+          win[r][5] = cur[at + 4] * sc;
+          const uint2 cm = *reinterpret_cast<const uint2*>(sCode + at);
+          cw[r][0] = sCode[at - 1];
+          cw[r][1] = cm.x & 0xffffu; cw[r][2] = cm.x >> 16;
+          cw[r][3] = cm.y & 0xffffu; cw[r][4] = cm.y >> 16;
+          cw[r][5] = sCode[at + 4];
+        }
+        float p[4];
+        ep_gather_any(u, cu, qru, cw, win, p);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          p[j] = p[j] * lt[sLX[cw[1][j + 1]] >> 2];
+          if (x0 + j >= W) p[j] = 0.0f;
+          m = fmaxf(m, p[j]);
+        }
+        const f4a out = {p[0], p[1], p[2], p[3]};
+        *reinterpret_cast<f4a*>(nxt + (y + 1) * ps + 4 + x0) = out;
+      }
+      m = wave_max(m);
+      if (lane == 0) red[44 + wave] = m;
+      __syncthreads();
+      m = fmaxf(fmaxf(red[44], red[45]), fmaxf(red[46], red[47]));
+      {
+        float* t = cur;
+        cur = nxt;
+        nxt = t;
+      }
+      const uint32_t mb = __float_as_uint(m);
+      if (!(m > 0.0f) || mb >= 0x7f800000u) {
+        status = 2;  // belief lost: the stored belief stays raw
+        steps = k + 1;
+        sc = 1.0f;
+      } else {
+        int e2 = (int)(mb >> 23) - 127;
+        e2 = e2 < -126 ? -126 : e2 > 126 ? 126 : e2;
+        sc = __uint_as_float((uint32_t)(127 - e2) << 23);
+        // 6. goal
+        if (sy * W + sx == a.goal) { status = 1; steps = k + 1; }
+      }
+    }
+
+    // the episode's results, and its stored belief (each lane its own quads;
+    // an episode that took no step reads the b0 image, behind the barrier above)
+    if (tid == 0) {
+      a.steps[e] = steps;
+      a.status[e] = (uint8_t)status;
+      a.cost[e] = G;
+      a.final_cell[e] = sy * W + sx;
+    }
+    float* bo = a.beliefs + (long long)e * NP;
+    PP2_EP_QUADS(i0, y, x0) {
+      f4a v = *reinterpret_cast<const f4a*>(cur + (y + 1) * ps + 4 + x0);
+      // (sc = 1: b0 or a raw update, stored as it is -- a multiply would flush
+      // b0's subnormals)
+      if (sc != 1.0f) { v[0] = v[0] * sc; v[1] = v[1] * sc; v[2] = v[2] * sc; v[3] = v[3] * sc; }
+      *reinterpret_cast<f4a*>(bo + i0) = v;
+    }
+  }
+}
+
+#undef PP2_EP_QUADS
+
+}  // namespace
+
+hipError_t launch_episode_qplanes(hipStream_t st, const Geom& g, const uint16_t* code,
+                                  const float* rows, int E, const float* J, float* Q, int ncus) {
+  const size_t lds = (size_t)lds_span(rows_floats(E, true)) * sizeof(float);
+  if (lds > kDictLdsMaxBytes) return hipErrorInvalidValue;
+  static unsigned long long attr = 0;
+  allow_lds(reinterpret_cast<const void*>(&k_episode_qplanes), attr);
+  const int nblocks = cells_grid(g, 4);
+  const int cap = ncus > 0 ? 4 * ncus : nblocks;
+  hipLaunchKernelGGL(k_episode_qplanes, dim3(nblocks < cap ? nblocks : cap), dim3(kBlock), lds, st,
+                     g, code, rows, E, J, nblocks, Q);
+  return hipGetLastError();
+}
+
+hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups) {
+  const long long bytes = episode_lds_bytes(a.g, a.E);
+  if (bytes > (long long)kDictLdsMaxBytes || workgroups < 1) return hipErrorInvalidValue;
+  if (policy == 1) {
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<1>), attr);
+    hipLaunchKernelGGL(k_episodes<1>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
+  } else {
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<0>), attr);
+    hipLaunchKernelGGL(k_episodes<0>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace pp2

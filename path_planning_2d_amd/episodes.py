@@ -1,0 +1,158 @@
+"""Batched closed-loop policy episodes (include/pp2.h "episodes").
+
+``EpisodeBatch`` runs E simulated robots under a control policy -- the
+belief-mode policy of the reference MDP node or the QMDP policy -- each with
+its own belief, for up to ``horizon`` steps in one kernel launch, and returns
+how the policy did: steps to the goal, status and discounted cost per episode.
+Everything runs in libpp2_hip.so; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import call
+from .core import GridContext, _f32, _u8
+
+MAX_EPISODES = 131072
+MAX_HORIZON = 4096
+
+STATUS_HORIZON = 0   # still running after the last step
+STATUS_GOAL = 1      # the true robot reached the goal
+STATUS_LOST = 2      # the belief update left no finite positive value
+
+
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+class EpisodeBatch:
+    """E closed-loop episodes over an unsharded ``GridContext`` with a model,
+    solved (or at least current) MDP values and an active coded model."""
+
+    def __init__(self, ctx: GridContext, episodes: int, horizon: int,
+                 record_trace: bool = False):
+        episodes, horizon = int(episodes), int(horizon)
+        if not 1 <= episodes <= MAX_EPISODES:
+            raise ValueError(f"episodes {episodes} outside 1..{MAX_EPISODES}")
+        if not 1 <= horizon <= MAX_HORIZON:
+            raise ValueError(f"horizon {horizon} outside 1..{MAX_HORIZON}")
+        self._h = None
+        self.ctx = ctx
+        self.episodes = episodes
+        self.horizon = horizon
+        self.record_trace = bool(record_trace)
+        self.cells = ctx.cells
+        self.policy = None
+        h = C.c_void_p()
+        call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
+             int(self.record_trace))
+        self._h = h
+
+    # ------------------------------------------------------------ lifetime
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            call("pp2_episodes_destroy", self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------ running
+    @staticmethod
+    def check_run_args(cells: int, episodes: int, policy, b0, start_cells, seed):
+        """Validated (policy, b0, start_cells, seed) of a run; raises ValueError
+        on anything the library would reject (and never calls it)."""
+        if isinstance(policy, str):
+            if policy not in GridContext._POLICIES:
+                raise ValueError(f"unknown control policy {policy!r}")
+            policy = GridContext._POLICIES[policy]
+        if policy not in (GridContext.CONTROL_MODE, GridContext.CONTROL_QMDP):
+            raise ValueError(f"unknown control policy {policy!r}")
+        b0 = np.ascontiguousarray(b0, np.float32).reshape(-1)
+        if b0.size != cells:
+            raise ValueError(f"b0 has {b0.size} cells, the grid {cells}")
+        if not (np.isfinite(b0).all() and (b0 >= 0).all() and not np.signbit(b0).any()):
+            raise ValueError("b0 must be finite and >= +0 everywhere")
+        start = np.asarray(start_cells)
+        if start.ndim != 1 or start.size != episodes:
+            raise ValueError(f"start_cells must hold {episodes} cells")
+        if not np.issubdtype(start.dtype, np.integer):
+            raise ValueError("start_cells must be integers")
+        if start.size and (start.min() < 0 or start.max() >= cells):
+            raise ValueError(f"start_cells outside [0, {cells})")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must fit 64 bits")
+        return int(policy), b0, np.ascontiguousarray(start, np.int32), seed
+
+    def run(self, policy, b0, start_cells, seed: int = 0):
+        """Enqueue one batch: every episode starts from belief ``b0`` with its
+        true robot at ``start_cells[e]`` (``y * W + x``).  Asynchronous."""
+        policy, b0, start, seed = self.check_run_args(self.cells, self.episodes, policy, b0,
+                                                      start_cells, seed)
+        call("pp2_episodes_run", self._h, policy, C.c_uint64(seed), _f32(b0), _i32(start))
+        self.policy = policy
+        return self
+
+    def results(self) -> dict:
+        """steps, status, cost, final_cell of every episode (synchronises)."""
+        E = self.episodes
+        steps = np.empty(E, np.int32)
+        status = np.empty(E, np.uint8)
+        cost = np.empty(E, np.float32)
+        final = np.empty(E, np.int32)
+        call("pp2_episodes_results", self._h, _i32(steps), _u8(status), _f32(cost), _i32(final))
+        return {"steps": steps, "status": status, "cost": cost, "final_cell": final}
+
+    def trace(self) -> dict:
+        """The last run's per-step record, [horizon, E] arrays (qsums
+        [horizon, E, 9]; only for QMDP runs, mode_cells only for mode runs).
+        Steps not taken hold 255, 255, -1, 0, -1."""
+        sh = (self.horizon, self.episodes)
+        a = np.empty(sh, np.uint8)
+        z = np.empty(sh, np.uint8)
+        cells = np.empty(sh, np.int32)
+        q = np.empty(sh + (9,), np.float32)
+        mode = np.empty(sh, np.int32)
+        call("pp2_episodes_trace", self._h, _u8(a), _u8(z), _i32(cells), _f32(q), _i32(mode))
+        return {"actions": a, "observations": z, "cells": cells, "qsums": q, "mode_cells": mode}
+
+    def belief(self, e: int) -> np.ndarray:
+        """The stored (power-of-two scaled) belief of episode ``e`` after the run."""
+        b = np.empty(self.cells, np.float32)
+        call("pp2_episodes_get_belief", self._h, int(e), _f32(b))
+        return b
+
+    def qplanes(self) -> np.ndarray:
+        """Q[hw, 9] of the last run: the sweep's cost of every action from the J
+        the run read."""
+        q = np.empty((self.cells, 9), np.float32)
+        call("pp2_episodes_get_q", self._h, _f32(q))
+        return q
+
+    def info(self) -> dict:
+        lds, wgs, th = C.c_int(0), C.c_int(0), C.c_int(0)
+        call("pp2_episodes_info", self._h, C.byref(lds), C.byref(wgs), C.byref(th))
+        return {"lds_bytes": lds.value, "workgroups": wgs.value, "threads": th.value}
+
+    def summary(self) -> dict:
+        """Success rate, mean steps of the successful episodes (nan if none)
+        and mean discounted cost of the last run."""
+        r = self.results()
+        ok = r["status"] == STATUS_GOAL
+        return {"episodes": self.episodes,
+                "success_rate": float(ok.mean()),
+                "mean_steps": float(r["steps"][ok].mean()) if ok.any() else float("nan"),
+                "mean_cost": float(r["cost"].astype(np.float64).mean()),
+                "lost": int((r["status"] == STATUS_LOST).sum())}

@@ -254,6 +254,24 @@ def action_parity(acts_a, vals_a, acts_b, vals_b) -> dict:
             "first_mismatch": int(bad[0]) if bad.size else None}
 
 
+def sample_cells(b0: np.ndarray, n: int, seed: int = 5) -> np.ndarray:
+    """n start cells (int32, ``y * W + x``) drawn from the belief ``b0`` with
+    splitmix64(seed): rollout_trajectories' inverse-CDF rule (the float64
+    cumulative sum, one draw per cell, never a cell of zero belief)."""
+    b = np.asarray(b0, np.float32).reshape(-1)
+    cdf = np.cumsum(b.astype(np.float64))
+    if not cdf[-1] > 0:
+        raise ValueError("the belief has no positive mass")
+    rng = SplitMix64(seed)
+    out = np.empty(n, np.int32)
+    for c in range(n):
+        cell = int(min(np.searchsorted(cdf, rng.u01() * cdf[-1], side="right"), b.size - 1))
+        while b[cell] <= 0:
+            cell -= 1
+        out[c] = cell
+    return out
+
+
 def rollout_trajectories(grid: np.ndarray, belief: np.ndarray, copies: int, depth: int,
                          seed: int = 5):
     """(us, zs) of shape [depth, copies] for batched rollouts: each copy draws a
