@@ -28,7 +28,9 @@
 //     ring slot t % kResidentRing (no tile runs more than one block ahead of
 //     the slowest, so a slot is never rewritten while a block start reads it);
 //     in the whole-row instance only the steps whose slot is read -- the one
-//     before a block start and the last -- compute partials at all;
+//     before a block start and the last -- compute partials at all, and the
+//     step before a block start publishes them and arrives right after its
+//     gather, a backup ahead of the step's end (PP2_RES_EARLY);
 //   * the last step stores b, J and A for the whole grid (non-temporal) and its
 //     partials to the context's pending buffer -- b and J into the OTHER
 //     ping-pong buffers, so the run's inputs survive it.
@@ -487,6 +489,17 @@ __device__ __forceinline__ int xch_gran(int ntiles, int wpr, int slot, int tl, i
 #ifndef PP2_RES_XCD_PLAIN
 #define PP2_RES_XCD_PLAIN 1
 #endif
+// The whole-row loop's early arrival (k_loop_resident, `early`): 0 the late
+// order, 1 a workgroup barrier before thread 0's add, 2 an LDS wave count
+// whose last adder signals.
+#ifndef PP2_RES_EARLY
+#define PP2_RES_EARLY 2
+#endif
+// The whole-row loop's reducing wave at a block start: 1 wave 0, 0 the
+// interior wave of the other instances.
+#ifndef PP2_RES_REDW0
+#define PP2_RES_REDW0 1
+#endif
 #ifndef PP2_RES_XCD_AUX
 #define PP2_RES_XCD_AUX 0  // the same-XCD stores' cache policy (0 plain, 1 sc0, 2 nt)
 #endif
@@ -895,6 +908,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // or not its rows cross a tile edge)
   unsigned use[2] = {a.slot_use[0], a.slot_use[1] + 1u};
   PP2_RP(5);
+  if constexpr (kSweepPipe && PP2_RES_EARLY == 2) {
+    if (threadIdx.x == 0) sS[1] = 0.0f;  // (the early arrivals' wave count)
+  }
   // step 0's input mass (k_sum_finalize's tree: lane-strided quads in
   // ascending order, then the butterfly)
   if (red0) {
@@ -925,8 +941,19 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // interior one (row 1, not a side wave; SIMD 1) when the tile has interior
   // rows, so that the reduction overlaps the edge waves' hand-off and compute
   // instead of following them on wave 0 (an edge wave)
-  const int redw = a.rt >= 3 && wpr >= 4 ? wpr + 1 : 0;
+  // The whole-row instance (PP2_RES_REDW0): wave 0 after all.  With the
+  // arrivals out early the chain that is left starts when the reducing wave
+  // has computed its quad, and the tile's first row, which computes with
+  // issue priority on rows the tile above published early, is done first
+  // (an interior wave is among the last; the tile's last row waits longest).
+  const int redw = kSweepPipe && PP2_RES_REDW0 != 0 ? 0 : a.rt >= 3 && wpr >= 4 ? wpr + 1 : 0;
   unsigned arrivals = a.arrive_base;
+  // early arrivals, form (b): the tile's valid waves (each stores a partial)
+  // and their LDS count so far, sS[1] (zeroed in the prologue)
+  const unsigned nvw = kSweepPipe ? (unsigned)(std::min(a.rt, rows - trow * a.rt) * wpr) : 0u;
+  unsigned early_n = 0u;
+  (void)nvw;
+  (void)early_n;
   int shift = 0;  // shard runs: the power-of-two shifts of the block starts so far
   // Lagged shard block starts (shard mode 2; shards run kstep0 = 0, so block
   // starts fall on multiples of depth).  The shift of the block start at T
@@ -996,6 +1023,61 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     // timed on the whole-row instance only.)
     const bool arrive = (a.kstep0 + t + 1) % a.depth == 0;
     const bool mass = !kSweepPipe || arrive || last;
+    // ---- early arrival (the whole-row instance).  On an arrive step whose
+    // belief is not scaled (no block start, not a launch's first step with a
+    // pending normalisation: inv == 1) the quad, and with it the wave's mass
+    // partial, is final right after the gather.  The partial and the tile's
+    // arrival go out there, before the backup, so that the grid-wide chain of
+    // the next step's block start (drain, add, poll, the partials' loads)
+    // runs under this step's backup as well.  Kept from the late order:
+    //   * one add per tile per arrive step, so the arrival targets
+    //     (arrivals += ntiles) and the host's arrival base do not change;
+    //   * ring slot t % kResidentRing is still written during step t, only
+    //     earlier in it; its previous reader was the block start kResidentRing
+    //     steps back, and every tile left that one before any tile could pass
+    //     the block start after it (depth <= kResidentRing - 2; at depth 2
+    //     the slot's last reader was 16 block starts ago);
+    //   * the partial is the same sum ((p0 + p1) + p2) + p3 of the same
+    //     values (p * 1 == p) through the same wave_sum, so the reduction
+    //     reads the late order's bits;
+    //   * the hand-off form (MI355X_MICROARCH.md, visibility table row 1):
+    //     every storing wave drains its sc1 partial, and one lane signals for
+    //     the workgroup after every wave's drain;
+    //   * no new wait: the error word and the bounded waits work as before.
+    // A step that is both arrive and block start (depth 1), the scaled first
+    // step and the last step keep the late order.
+    const bool early = kSweepPipe && PP2_RES_EARLY != 0 && arrive && !bs && !last &&
+                       !(t == 0 && start0);
+    auto early_arrive = [&]() {
+      float s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s += p[k];
+      const float v = wave_sum(s);
+      if (lane == 0 && pi < a.nparts)
+        st_flag(reinterpret_cast<unsigned*>(a.ring + (size_t)(t % kResidentRing) * a.nparts + pi),
+                __float_as_uint(v));
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if PP2_RES_EARLY == 1
+      // (a) a workgroup barrier, then thread 0's add.  The tile's invalid
+      // waves (a partial last tile) join the barrier below, outside valid.
+      __syncthreads();
+      if (threadIdx.x == 0)
+        __hip_atomic_fetch_add(a.sync + kResidentSyncArrive, 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+#else
+      // (b) each valid wave counts itself in LDS after its drain; the wave
+      // whose add comes last (the tile's nvw-th of this step) signals
+      early_n += nvw;
+      if (lane == 0) {
+        const unsigned old = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(sS + 1), 1u,
+                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (old + 1u == early_n)
+          __hip_atomic_fetch_add(a.sync + kResidentSyncArrive, 1u, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+      }
+      asm volatile("" ::: "memory");
+#endif
+    };
     // one quad of step t: window rows from LDS (step t-1), the neighbour rows
     // of step t-1, or 0 off the grid; b' before the scale in p
     auto step_quad = [&]() {
@@ -1056,7 +1138,12 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         for (int i = 0; i < (kClsSlots + 1) / 2; ++i) asm volatile("" : "+v"(creg.lh[i]));
         belief_any_regs(u, creg, lx4, z, wb, p);
       }
-      else if constexpr (kSweepPipe) belief_any_pre<TR>(u, x0, lx4, z, wb, crow, p);
+      else if constexpr (kSweepPipe) {
+        belief_any_pre<TR>(u, x0, lx4, z, wb, crow, p);
+        if constexpr (PP2_RES_EARLY != 0) {
+          if (early) early_arrive();
+        }
+      }
       else belief_any<TR>(u, sP, prows, ps, ty, x0, lx4, z, wb, p);
       float jn[9][4];  // grid stencil offset i = 3 (dy + 1) + dx + 1
 #pragma unroll
@@ -1078,7 +1165,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     auto finish_quad = [&]() {
 #pragma unroll
       for (int k = 0; k < 4; ++k) p[k] = p[k] * inv;
-      if (mass) {
+      if (mass && !early) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) local += p[k];
       }
@@ -1095,6 +1182,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       step_quad();
       if (!bs || lag) finish_quad();
     }
+#if PP2_RES_EARLY == 1
+    else if (early) __syncthreads();  // early_arrive's barrier (a wave-uniform branch)
+#endif
     if (bs && !lag) {
       if (wave == redw) {
         arrivals += a.ntiles;
@@ -1117,14 +1207,14 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     if (last) break;  // the last step's outputs are stored after the loop
     ++use[ci];
     // ---- mass partials of step t (dense map), sc1 into the ring
-    if (mass) {
+    if (mass && !early) {
       const float v = wave_sum(local);
       if (lane == 0 && pi < a.nparts)
         st_flag(reinterpret_cast<unsigned*>(a.ring + (size_t)(t % kResidentRing) * a.nparts + pi),
                 __float_as_uint(v));
     }
-    // ---- (every wave drained before the arrival)
-    if (arrive) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ---- (every wave drained before the arrival; an early arrival is out already)
+    if (arrive && !early) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (wave == redw && lag_start(t + 1)) {  // the lagged mass for the next step's block start
       float S;
       if (red_ok) {  // (the drain above completed the copy)
@@ -1145,7 +1235,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
 #ifndef PP2_RES_NOBAR
     __syncthreads();  // also: this step's LDS writes before the next step's reads
 #endif
-    if (arrive && threadIdx.x == 0)
+    if (arrive && !early && threadIdx.x == 0)
       __hip_atomic_fetch_add(a.sync + kResidentSyncArrive, 1u, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
     PP2_RT(3);
