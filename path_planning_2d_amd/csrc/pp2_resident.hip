@@ -168,7 +168,9 @@ __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t
 // X bounds the mass of step t-1 and the scaled mass stays below 2^121 --
 // it lands in [2^120 * (decay over depth steps), 2^121).  The target 2^120
 // (not 2^96) keeps the headroom of the non-lagged scheme over the up to
-// 2 x depth steps of decay between two such shifts.
+// 2 x depth steps of decay between two such shifts.  The launch's first block
+// start has no such S: it takes the scale of the launch's first step, which
+// bounds every later mass (pow2_shift_lagged(bscale, 0) = 24).
 __device__ __forceinline__ int pow2_shift_lagged(float S, int prev) {
   if (!(S > 0.0f) || !(S < FLT_MAX)) return 0;
   const int e = (int)((__float_as_uint(S) >> 23) & 0xffu) - 127;
@@ -1008,7 +1010,16 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         if (lag_start(t + 2)) arr_v = ld_flag(a.sync + kResidentSyncArrive);
       }
       if (bs) {  // the shift from sS[0] (the end of step t-1), before the gather
-        const int sh = t - 1 - a.depth >= 0 ? pow2_shift_lagged(sS[0], sh_prev) : 0;
+        // The launch's first block start (t == depth) has no mass a block
+        // back.  Its bound is the launch's own normalisation: step 0 divided
+        // by the global mass and scaled by bscale, so every later mass is
+        // below 2 bscale and the shift is the constant 120 - ilogb(bscale)
+        // (24).  Without it the first 2 depth steps of a launch decay on the
+        // 2^96 of step 0 alone, and at P(z) ~ 1e-2 per step cells flush to
+        // zero that the waited scheme keeps (tests/test_gpu_loop_coverage.py).
+        const int sh = t - 1 - a.depth >= 0 ? pow2_shift_lagged(sS[0], sh_prev)
+                       : start0 && (a.in_partials || a.in_sum) ? pow2_shift_lagged(a.bscale, 0)
+                                                               : 0;
         sh_prev = sh;
         shift += sh;
         inv = pow2f(sh);

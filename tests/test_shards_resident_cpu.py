@@ -14,7 +14,9 @@ of two chosen from the view's own mass (exact, so shards may pick different
 shifts) -- the mass of the previous step (PP2_TUNE_SHARD_LAG 0), or, lagged
 (the default), the mass of the step before the previous block start times
 the shift applied there, into [2^120, 2^121) (pp2_resident.hip
-pow2_shift_lagged; the launch's first block start keeps the input's scale).  At a block boundary each rank posts its {owned mass, total shift,
+pow2_shift_lagged; the launch's first block start, with no mass a block
+back, takes the 2^96 of step 0 as its bound: a shift of 24).  At a block
+boundary each rank posts its {owned mass, total shift,
 lost} record and sends it to every other rank in the same point-to-point
 group as the halo rows (one RCCL round per block); at the end of the call the
 records are all-reduced.  Every rank then rebases its rows -- a halo row by
@@ -161,8 +163,8 @@ def _worker(rank, world, port, name, steps, e, depth, lag, result_q):
                         sh = _pow2_shift(b.astype(np.float64).sum())
                     elif t - 1 - depth >= 0:
                         sh = _pow2_shift_lagged(vmass[t - 1 - depth], sh_prev)
-                    else:
-                        sh = 0
+                    else:  # the launch's first block start: step 0's scale bounds the mass
+                        sh = _pow2_shift_lagged(np.float32(2.0 ** 96), 0)
                     sh_prev = sh
                     shift += sh
                     inv = np.float32(2.0 ** sh)
