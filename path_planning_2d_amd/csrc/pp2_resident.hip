@@ -220,6 +220,17 @@ __device__ __forceinline__ float wave_reduce_partials_sc1(const float* p, int n)
 // source cell at grid offset (oy - 1, ox) sits in window row ox + 1, window
 // column k + oy of the lane's quad cell k; the terms keep the grid's
 // ascending-s order (the same fmaf chain).
+// sup_slot as a table, for the whole-row gather's two unrolled loops (reads,
+// then fmafs): a constant index folds, where sup_slot's own search loop,
+// called twice per term, was left a run-time loop over kSup in some cases
+struct SupSlots {
+  int s[9][9];
+  constexpr SupSlots() : s{} {
+    for (int u = 0; u < 9; ++u)
+      for (int i = 0; i < 9; ++i) s[u][i] = sup_slot(u, i);
+  }
+};
+constexpr SupSlots kSupSlot{};
 template <bool TR>
 constexpr bool belief_row_used(int U, int r) {
   for (int s = 0; s < 9; ++s)
@@ -232,6 +243,16 @@ constexpr bool belief_row_used(int U, int r) {
 struct ClassRows {
   uint32_t m[3], e[3];
 };
+// The step's serial chain (A/B builds: 0 keeps the earlier form)
+#ifndef PP2_RES_GATHER1
+#define PP2_RES_GATHER1 1  // the whole-row gather's table reads in one LDS round trip
+#endif
+#ifndef PP2_RES_TRAJ_SGPR
+#define PP2_RES_TRAJ_SGPR 1  // (u, z) from a trajectory word held in an SGPR
+#endif
+#ifndef PP2_RES_PHASE_CTR
+#define PP2_RES_PHASE_CTR 1  // the block phase as a counter, not two % depth per step
+#endif
 __device__ __forceinline__ void load_class_rows(const uint8_t* prow, int ps, int x0, ClassRows& c) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -279,6 +300,40 @@ __device__ __forceinline__ void belief_fact(const uint8_t* prow, int ps, int x0,
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) p[k] = 0.0f;
+  if constexpr (PRE && PP2_RES_GATHER1) {
+    // The whole-row instance: the action's QR values (one per cell and
+    // support offset, <= 16 a quad) and the quad's four LT values are all
+    // issued before the first fmaf, the order pinned by a scheduling barrier
+    // -- one LDS round trip.  Left to itself the compiler interleaves the
+    // reads with their fmafs through two or three destination registers, and
+    // each action's case waits lgkmcnt(0) four to six times, each time behind
+    // a read it has just issued.  The same fmaf chains on the same values.
+    float tq[9][4], lz[4];
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+      const int wr = TR ? s % 3 : s / 3, wc = TR ? s / 3 - 1 : s % 3 - 1;
+      const int sl = kSupSlot.s[U][8 - s];
+      if (sl < 0) continue;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        tq[s][k] = *reinterpret_cast<const float*>(qr + 4 * sl + cb[wr][k + 1 + wc]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      lz[k] = *reinterpret_cast<const float*>(lt + __builtin_amdgcn_ubfe(lx4, 8 * k, 8));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+      const int wr = TR ? s % 3 : s / 3, wc = TR ? s / 3 - 1 : s % 3 - 1;
+      const int sl = kSupSlot.s[U][8 - s];
+      if (sl < 0) continue;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p[k] = __builtin_fmaf(tq[s][k], win.v[wr][k + 1 + wc], p[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = p[k] * lz[k];
+    return;
+  }
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
     // window row and column offset of grid offset s
@@ -634,7 +689,8 @@ __device__ __forceinline__ void row_quad(const float (&m)[4], float e, float (&v
 }
 
 template <int CAP>
-struct Trajectory {
+struct alignas(4) Trajectory {  // (read as words: CAP % 4 == 0)
+  static_assert(CAP % 4 == 0, "the loop reads the trajectory as 32-bit words");
   uint8_t uz[CAP];  // u | z << 4 per step
 };
 
@@ -981,8 +1037,25 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   uint32_t arg[4] = {0u, 0u, 0u, 0u};
   PP2_RP(2);
 
+  // The trajectory as aligned words through a uniform index (s_load_dword; a
+  // byte indexed by t is a vector load and a vmcnt(0) at the step's head,
+  // behind the previous step's publish stores): steps 4w .. 4w + 3 are the
+  // bytes of word w, held in an SGPR and reloaded before the end-of-step
+  // barrier of step 4w + 3 (below), never past the argument.
+  const uint32_t* const trw = reinterpret_cast<const uint32_t*>(tr.uz);
+  uint32_t uzw = trw[0];
+  // (kstep0 + t) % depth, advanced per step
+  int ph = a.kstep0 % a.depth;
+  (void)trw;
+  (void)uzw;
+  (void)ph;
   for (int t = 0; t < a.n; ++t) {
+#if PP2_RES_TRAJ_SGPR
+    const uint32_t uzb = (uzw >> (8 * (t & 3))) & 0xffu;
+    const int u = uzb & 15, z = uzb >> 4;
+#else
     const int u = tr.uz[t] & 15, z = tr.uz[t] >> 4;
+#endif
     const int ci = t & 1, co = ci ^ 1;
     const bool last = t == a.n - 1;
     // ---- a block start inside the run needs the exact mass of step t-1's
@@ -991,7 +1064,12 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     // than the owned ones).  The step's gather and backup go first: the mass
     // only scales the gathered quad, so the grid-wide arrival wait overlaps
     // this tile's compute instead of preceding it.
+#if PP2_RES_PHASE_CTR
+    const bool bs = t > 0 && ph == 0;
+    ph = ph + 1 == a.depth ? 0 : ph + 1;  // step t + 1's phase
+#else
     const bool bs = t > 0 && (a.kstep0 + t) % a.depth == 0;
+#endif
     if (t > 0 && !bs) inv = 1.0f;
     if (lag) {
       if (wave == redw) {
@@ -1032,7 +1110,11 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     // loop, so the whole-row instance computes no mass partial on the other
     // steps.  (The other instances keep the partial per step: the change was
     // timed on the whole-row instance only.)
+#if PP2_RES_PHASE_CTR
+    const bool arrive = ph == 0;
+#else
     const bool arrive = (a.kstep0 + t + 1) % a.depth == 0;
+#endif
     const bool mass = !kSweepPipe || arrive || last;
     // ---- early arrival (the whole-row instance).  On an arrive step whose
     // belief is not scaled (no block start, not a launch's first step with a
@@ -1243,6 +1325,11 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       }
       if (lane == 0) sS[0] = S;
     }
+#if PP2_RES_TRAJ_SGPR
+    // steps t + 1 .. t + 4's word, under the barrier's wait (after the backup:
+    // a scalar load among its counted lgkmcnt waits would make them drains)
+    if (((t + 1) & 3) == 0 && t + 1 < CAP) uzw = trw[(t + 1) >> 2];
+#endif
 #ifndef PP2_RES_NOBAR
     __syncthreads();  // also: this step's LDS writes before the next step's reads
 #endif
