@@ -1,10 +1,11 @@
 /*
- * pp2_episodes_demo.c -- evaluating the two control policies through the C ABI
- * alone (include/pp2.h "episodes"): solve the MDP of sparse_map_100x40, then
- * run a batch of simulated closed-loop episodes under the belief-mode policy
- * and under the QMDP policy, each in one launch, and print success rate, mean
- * steps to the goal and mean discounted cost.  Plain C99, linked against
- * libpp2_hip.so.
+ * pp2_episodes_demo.c -- evaluating the four control policies through the C ABI
+ * alone (include/pp2.h "episodes"): solve the MDP, the FIB alphas and a small
+ * PBVI set of sparse_map_100x40, then run a batch of simulated closed-loop
+ * episodes under the belief-mode policy, the QMDP policy, the FIB-greedy and
+ * the PBVI-greedy policy -- the same robots, seed and cost scale, each in one
+ * launch -- and print success rate, mean steps to the goal and mean discounted
+ * cost.  Plain C99, linked against libpp2_hip.so.
  *
  *   ./pp2_episodes_demo [map.npy]     (default tests/golden/maps/sparse_map_100x40.npy,
  *                                      from the repository root); exit status 0 on success
@@ -25,7 +26,7 @@
     }                                                                              \
   } while (0)
 
-enum { H = 40, W = 100, EPISODES = 2048, HORIZON = 128 };
+enum { H = 40, W = 100, EPISODES = 2048, HORIZON = 128, PBVI_SET = 32 };
 
 /* the uint8 payload of a version-1 .npy file of H * W bytes */
 static int load_map(const char* path, uint8_t* map) {
@@ -70,16 +71,25 @@ int main(int argc, char** argv) {
   int sweeps = 0;
   double norm = 0.0;
   CHECK(pp2_mdp_solve(ctx, 0, &sweeps, &norm));
+  int fib_sweeps = 0;
+  float fib_norm = 0.0f;
+  CHECK(pp2_fib_solve(ctx, 0, &fib_sweeps, &fib_norm));
+  CHECK(pp2_pbvi_solve(ctx, b0, PBVI_SET, 1, NULL));
   pp2_episodes* ep = NULL;
   CHECK(pp2_episodes_create(&ep, ctx, EPISODES, HORIZON, 0));
   int lds = 0, wgs = 0, threads = 0;
   CHECK(pp2_episodes_info(ep, &lds, &wgs, &threads));
-  printf("pp2_episodes_demo: MDP solved in %d sweeps; %d episodes x %d steps, %d workgroups of "
-         "%d threads, %d B of LDS each\n", sweeps, EPISODES, HORIZON, wgs, threads, lds);
-  const int policies[2] = {PP2_CONTROL_MODE, PP2_CONTROL_QMDP};
-  const char* names[2] = {"mode", "QMDP"};
-  for (int p = 0; p < 2; ++p) {
-    CHECK(pp2_episodes_run(ep, policies[p], 2024, b0, start));
+  printf("pp2_episodes_demo: MDP solved in %d sweeps, FIB in %d, PBVI with %d beliefs; %d episodes "
+         "x %d steps, %d workgroups of %d threads, %d B of LDS each\n", sweeps, fib_sweeps,
+         PBVI_SET, EPISODES, HORIZON, wgs, threads, lds);
+  /* mode and QMDP read J and A, the alpha runs the FIB / PBVI vectors */
+  const int policies[4] = {PP2_CONTROL_MODE, PP2_CONTROL_QMDP, PP2_ALPHA_FIB, PP2_ALPHA_PBVI};
+  const char* names[4] = {"mode", "QMDP", "FIB-greedy", "PBVI-greedy"};
+  for (int p = 0; p < 4; ++p) {
+    if (p < 2)
+      CHECK(pp2_episodes_run(ep, policies[p], 2024, b0, start));
+    else
+      CHECK(pp2_episodes_run_alpha(ep, policies[p], 2024, b0, start));
     CHECK(pp2_episodes_results(ep, steps, status, cost, NULL));
     int reached = 0, lost = 0;
     double sum_steps = 0.0, sum_cost = 0.0;

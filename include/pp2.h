@@ -553,7 +553,27 @@ int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
  * (pads add +0): 256 lanes; lane t from +0, for j = 0, 1, .. and k = 0..3 with
  * i = 1024j + 4t + k < NP: acc = acc + fl(b[i] * Q_u[i]); each group of 64
  * lanes folded by the xor butterfly 32, 16, 8, 4, 2, 1; then
- * ((w0 + w1) + w2) + w3. */
+ * ((w0 + w1) + w2) + w3.
+ *
+ * Alpha runs (pp2_episodes_run_alpha): the greedy policy of an alpha-vector
+ * set, K vectors alpha_k with an action each -- PP2_ALPHA_FIB: the context's
+ * current FIB alphas, K = 9, action of vector k = k (never solved: the zeros,
+ * valid); PP2_ALPHA_PBVI: the context's PBVI alpha vectors and their actions,
+ * K = S <= 4096.  An alpha run is pp2_episodes_run with step 1 replaced; steps
+ * 2-6, the random numbers, the results and the statuses are unchanged, and the
+ * cost G still accumulates the MDP cost C[s][u], so all four policies are
+ * compared on one scale.
+ *  1. control.  V_k = sum_i b[i] alpha_k[i] in the pinned Q-dot order above
+ *     with alpha_k in place of Q_u (separate roundings, flush-to-zero, over
+ *     the padded planes alpha_k[y*stride + x], pads +0); best = 0, then for
+ *     k = 1 .. K-1: if (V_best < V_k) best = k; u = action[best].  So the first
+ *     maximum wins, a NaN sum never displaces the incumbent and a NaN V_0 is
+ *     never displaced.  Non-finite alpha entries are not rejected: the
+ *     arithmetic above defines the result.
+ * A run reads the alpha set that is current when it is enqueued (stream
+ * ordered, as J and A): once per run it is repacked into planes [K][row][row
+ * stride], pads +0, allocated at the first alpha run and regrown when K grows
+ * (PP2_ENOMEM if that fails). */
 typedef struct pp2_episodes pp2_episodes;
 /* episodes 1..131072, horizon 1..4096; record_trace != 0 keeps the per-step
  * trace.  PP2_ESTATE: no model, a row shard or group member, coded model
@@ -579,10 +599,31 @@ int pp2_episodes_trace(pp2_episodes* ep, uint8_t* actions, uint8_t* observations
                        int32_t* cells, float* qsums, int32_t* mode_cells);
 /* the stored belief of one episode after the run (hw floats) */
 int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief);
-/* the Q planes of the last run as Q[hw][9] */
+/* the Q planes of the last run as Q[hw][9]; PP2_ESTATE after an alpha run,
+ * which builds none */
 int pp2_episodes_get_q(pp2_episodes* ep, float* Q);
-/* LDS bytes per workgroup, workgroups and threads per workgroup of a launch */
+/* LDS bytes per workgroup, workgroups and threads per workgroup of the last
+ * launch (before any run: of a MODE / QMDP launch; an alpha launch adds its
+ * scratch for K != 9) */
 int pp2_episodes_info(pp2_episodes* ep, int* lds_bytes, int* workgroups, int* threads);
+#define PP2_ALPHA_FIB  0   /* the context's current FIB alphas: K = 9, action of vector k = k */
+#define PP2_ALPHA_PBVI 1   /* the context's PBVI alpha vectors and their actions: K = S */
+/* pp2_episodes_run with the alpha-vector policy ("Alpha runs" above); b0 and
+ * start_cells as there.  PP2_EINVAL: unknown alpha_set, a PBVI action > 8, or
+ * the workgroup's LDS with the alpha scratch does not fit (all before any
+ * launch); PP2_ESTATE: PP2_ALPHA_PBVI without alpha vectors.  Afterwards
+ * pp2_episodes_trace returns actions, observations and cells as usual, qsums
+ * = the nine V_k (FIB runs; 0 for PBVI runs) and mode_cells = -1.
+ * Asynchronous. */
+int pp2_episodes_run_alpha(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
+                           const int32_t* start_cells);
+/* [horizon][episodes], either may be NULL: index of the winning vector and its
+ * sum; steps not taken: -1, 0.  PP2_ESTATE unless the last run was an alpha
+ * run, or without record_trace. */
+int pp2_episodes_trace_alpha(pp2_episodes* ep, int32_t* best_index, float* best_sum);
+/* the alpha set the last alpha run read: *count = K; alphas [K][hw], actions
+ * [K]; any may be NULL.  PP2_ESTATE unless the last run was an alpha run. */
+int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t* actions);
 
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):

@@ -1,7 +1,8 @@
 // pp2_episodes.cpp -- C ABI of the batched closed-loop policy episodes
 // (include/pp2.h "episodes").  Kernels: pp2_episodes.hip.  A run enqueues the
-// Q planes of the current J and one launch of the persistent episode kernel on
-// the context's stream; results, traces and beliefs are copied back on demand.
+// Q planes of the current J -- an alpha run the planes of the current FIB or
+// PBVI alpha vectors instead -- and one launch of the persistent episode kernel
+// on the context's stream; results, traces and beliefs are copied back on demand.
 #include <cstring>
 #include <vector>
 
@@ -15,8 +16,16 @@ struct pp2_episodes {
   int episodes = 0, horizon = 0;
   bool trace = false;
   int H = 0, W = 0, wp = 0;    // the geometry the buffers were sized for
-  int policy = -1;             // of the last run (-1: none yet)
-  int lds_bytes = 0, workgroups = 0;
+  int policy = -1;             // of the last run (-1: none yet; 2: an alpha run)
+  int alpha_set = -1;          // of the last run, if that was an alpha run
+  int lds_bytes = 0, workgroups = 0;  // of the last launch (before any: MODE / QMDP's)
+  int base_workgroups = 0;     // of a MODE / QMDP launch
+  float* d_alpha = nullptr;    // [alpha_cap][H][wp], from the first alpha run on
+  uint8_t* d_alpha_act = nullptr;  // [alpha_cap]
+  int alpha_cap = 0, alpha_k = 0;  // vectors allocated, vectors of the last alpha run
+  int32_t* d_trbest = nullptr;  // alpha traces, [horizon][E]
+  float* d_trbsum = nullptr;
+  unsigned acts_ok_version = 0;  // the context's pbvi_version whose actions were found <= 8
   float* d_q = nullptr;        // [9][H][wp]
   float* d_b0 = nullptr;       // [H][wp]
   int32_t* d_start = nullptr;  // [E]
@@ -79,6 +88,169 @@ int fetch(pp2_ctx* c, T* dst, const T* src, size_t n) {
   return PP2_OK;
 }
 
+constexpr int kPolicyAlpha = 2;  // launch_episodes' alpha-vector instance
+
+int check_ran_alpha(const pp2_episodes* ep, const char* fn) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (ep->policy != kPolicyAlpha)
+    return set_err(PP2_ESTATE, "%s: the last run was not an alpha run", fn);
+  return PP2_OK;
+}
+
+// persistent workgroups: as many as the CUs hold at once, at most one per episode
+int episode_workgroups(const pp2_ctx* c, int episodes, long long lds) {
+  int per_cu = (int)((long long)pp2::kDictLdsMaxBytes / lds);
+  per_cu = per_cu < 1 ? 1 : per_cu > pp2::kEpMaxPerCu ? pp2::kEpMaxPerCu : per_cu;
+  const long long cap = (long long)(c->ncus > 0 ? c->ncus : 256) * per_cu;
+  return (int)(episodes < cap ? episodes : cap);
+}
+
+// One run.  policy: PP2_CONTROL_MODE / PP2_CONTROL_QMDP, or kPolicyAlpha with
+// alpha_set PP2_ALPHA_FIB / PP2_ALPHA_PBVI (all checked by the callers).
+int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const float* b0,
+             const int32_t* start_cells) {
+  pp2_ctx* c = ep->ctx;
+  const bool alpha = policy == kPolicyAlpha;
+  // settles pending resident launches first: J and A below are the current ones
+  long long lds = 0;
+  CHECK(check_episode_ctx(c, ep, &lds));
+  const int H = ep->H, W = ep->W, wp = ep->wp, E = ep->episodes;
+  const size_t hw = (size_t)H * W;
+  // the alpha set: the context's current one
+  int K = 0, ld = 0;
+  const float* d_rows = nullptr;     // PBVI's flat rows
+  const uint8_t* d_acts = nullptr;   // ... and their actions
+  if (alpha) {
+    if (alpha_set == PP2_ALPHA_FIB) {
+      K = 9;
+    } else {
+      int Sp = 0;
+      CHECK(pbvi_alphas(c, &d_rows, &K, &Sp, &ld));
+      CHECK(pbvi_actions(c, &d_acts));
+      if (K > pp2::kEpAlphaMax)
+        return set_err(PP2_EINVAL, "%d alpha vectors (at most %d)", K, pp2::kEpAlphaMax);
+    }
+    lds = pp2::episode_alpha_lds_bytes(c->g, c->dict_n, K);
+    if (lds > (long long)pp2::kDictLdsMaxBytes)
+      return set_err(PP2_EINVAL,
+                     "a %d x %d belief with the alpha scratch needs %lld bytes of LDS per "
+                     "episode (at most %zu fit)",
+                     W, H, lds, pp2::kDictLdsMaxBytes);
+  }
+  for (size_t i = 0; i < hw; ++i) {
+    uint32_t bits;
+    std::memcpy(&bits, &b0[i], 4);
+    if (bits >= 0x7f800000u)  // negative (-0 too), infinite or NaN
+      return set_err(PP2_EINVAL, "b0[%zu] is not finite and >= +0", i);
+  }
+  for (int e = 0; e < E; ++e)
+    if (start_cells[e] < 0 || (size_t)start_cells[e] >= hw)
+      return set_err(PP2_EINVAL, "start_cells[%d] = %d outside [0, %zu)", e, start_cells[e], hw);
+  DeviceGuard dg(c->device);
+  // the staging vectors may still feed the previous run's copies
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t np = (size_t)H * wp, HE = (size_t)ep->horizon * E;
+  if (alpha) {
+    // a PBVI action the tables have no row for: before any launch.  Checked
+    // once per version of the set (a copy to the host and a synchronise), not
+    // once per run.
+    if (d_acts && ep->acts_ok_version != c->pbvi_version) {
+      std::vector<uint8_t> act((size_t)K);
+      HIPCHK(hipMemcpyAsync(act.data(), d_acts, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      for (int k = 0; k < K; ++k)
+        if (act[k] > 8)
+          return set_err(PP2_EINVAL, "action %u of alpha vector %d out of range", act[k], k);
+      ep->acts_ok_version = c->pbvi_version;
+    }
+    if (K > ep->alpha_cap) {  // (the stream is idle: nothing reads the old planes)
+      if (ep->d_alpha) (void)hipFree(ep->d_alpha);
+      if (ep->d_alpha_act) (void)hipFree(ep->d_alpha_act);
+      ep->d_alpha = nullptr;
+      ep->d_alpha_act = nullptr;
+      ep->alpha_cap = ep->alpha_k = 0;
+      CHECK(dev_alloc(&ep->d_alpha, (size_t)K * np, "alpha planes"));
+      CHECK(dev_alloc(&ep->d_alpha_act, (size_t)K, "alpha actions"));
+      ep->alpha_cap = K;
+    }
+    if (ep->trace && !ep->d_trbest) CHECK(dev_alloc(&ep->d_trbest, HE, "winner trace"));
+    if (ep->trace && !ep->d_trbsum) CHECK(dev_alloc(&ep->d_trbsum, HE, "winning-sum trace"));
+  }
+  ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
+  ep->workgroups = alpha ? episode_workgroups(c, E, lds) : ep->base_workgroups;
+  for (int y = 0; y < H; ++y)
+    std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
+  std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
+  HIPCHK(hipMemcpyAsync(ep->d_b0, ep->h_b0.data(), np * sizeof(float), hipMemcpyHostToDevice,
+                        c->stream));
+  HIPCHK(hipMemcpyAsync(ep->d_start, ep->h_start.data(), (size_t)E * sizeof(int32_t),
+                        hipMemcpyHostToDevice, c->stream));
+  if (ep->trace) {
+    // steps not taken: 255, 255, -1, 0, -1 (alpha runs: winner -1, its sum 0)
+    HIPCHK(hipMemsetAsync(ep->d_tru, 0xff, HE, c->stream));
+    HIPCHK(hipMemsetAsync(ep->d_trz, 0xff, HE, c->stream));
+    HIPCHK(hipMemsetAsync(ep->d_trcell, 0xff, HE * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(ep->d_trmode, 0xff, HE * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(ep->d_trq, 0, HE * 9 * sizeof(float), c->stream));
+    if (alpha) {
+      HIPCHK(hipMemsetAsync(ep->d_trbest, 0xff, HE * sizeof(int32_t), c->stream));
+      HIPCHK(hipMemsetAsync(ep->d_trbsum, 0, HE * sizeof(float), c->stream));
+    }
+  }
+  if (alpha) {
+    // the snapshot of the set: planes and actions, stream-ordered
+    const bool fib = alpha_set == PP2_ALPHA_FIB;
+    HIPCHK(pp2::launch_episode_alpha_planes(c->stream, c->g, fib ? &c->fib[c->fcur].v : nullptr,
+                                            d_rows, ld, K, ep->d_alpha, d_acts, ep->d_alpha_act));
+  } else {
+    HIPCHK(pp2::launch_episode_qplanes(c->stream, c->g, c->d_code, c->d_rows, c->dict_n,
+                                       c->J[c->jcur].v.p, ep->d_q, c->ncus));
+  }
+  pp2::EpisodeRun a{};
+  a.g = c->g;
+  a.E = c->dict_n;
+  a.code = c->d_code;
+  a.rows = c->d_rows;
+  a.rfact = c->d_rfact;
+  a.Q = ep->d_q;
+  a.A = c->A;
+  if (alpha) {
+    a.alpha = ep->d_alpha;
+    a.alpha_act = ep->d_alpha_act;
+    a.K = K;
+  }
+  a.b0 = ep->d_b0;
+  a.start = ep->d_start;
+  a.episodes = E;
+  a.horizon = ep->horizon;
+  a.seed = seed;
+  a.gamma = c->gamma;
+  a.goal = c->gy * W + c->gx;
+  a.steps = ep->d_steps;
+  a.status = ep->d_status;
+  a.cost = ep->d_cost;
+  a.final_cell = ep->d_final;
+  a.beliefs = ep->d_beliefs;
+  if (ep->trace) {
+    a.tr_u = ep->d_tru;
+    a.tr_z = ep->d_trz;
+    a.tr_cell = ep->d_trcell;
+    // the nine sums: QMDP's S_u, a FIB run's V_k
+    a.tr_q = policy == PP2_CONTROL_QMDP || (alpha && alpha_set == PP2_ALPHA_FIB) ? ep->d_trq
+                                                                                 : nullptr;
+    a.tr_mode = ep->d_trmode;
+    if (alpha) {
+      a.tr_best = ep->d_trbest;
+      a.tr_bsum = ep->d_trbsum;
+    }
+  }
+  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups));
+  ep->policy = policy;
+  ep->alpha_set = alpha ? alpha_set : -1;
+  if (alpha) ep->alpha_k = K;
+  return PP2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -90,7 +262,8 @@ int pp2_episodes_destroy(pp2_episodes* ep) {
   for (void* p : {(void*)ep->d_q, (void*)ep->d_b0, (void*)ep->d_start, (void*)ep->d_steps,
                   (void*)ep->d_final, (void*)ep->d_cost, (void*)ep->d_status,
                   (void*)ep->d_beliefs, (void*)ep->d_tru, (void*)ep->d_trz, (void*)ep->d_trcell,
-                  (void*)ep->d_trmode, (void*)ep->d_trq})
+                  (void*)ep->d_trmode, (void*)ep->d_trq, (void*)ep->d_alpha,
+                  (void*)ep->d_alpha_act, (void*)ep->d_trbest, (void*)ep->d_trbsum})
     if (p) (void)hipFree(p);
   delete ep;
   return PP2_OK;
@@ -117,11 +290,7 @@ int pp2_episodes_create(pp2_episodes** out, pp2_ctx* c, int episodes, int horizo
   ep->W = c->g.width;
   ep->wp = c->g.wp;
   ep->lds_bytes = (int)lds;
-  // persistent workgroups: as many as the CUs hold at once, at most one per episode
-  int per_cu = (int)((long long)pp2::kDictLdsMaxBytes / lds);
-  per_cu = per_cu < 1 ? 1 : per_cu > pp2::kEpMaxPerCu ? pp2::kEpMaxPerCu : per_cu;
-  const long long cap = (long long)(c->ncus > 0 ? c->ncus : 256) * per_cu;
-  ep->workgroups = (int)(episodes < cap ? episodes : cap);
+  ep->workgroups = ep->base_workgroups = episode_workgroups(c, episodes, lds);
   const size_t np = (size_t)ep->H * ep->wp, E = (size_t)episodes, HE = (size_t)horizon * E;
   auto fail = [&](int s) {
     pp2_episodes_destroy(ep);
@@ -156,72 +325,43 @@ int pp2_episodes_run(pp2_episodes* ep, int policy, uint64_t seed, const float* b
   if (!b0 || !start_cells) return set_err(PP2_EINVAL, "null argument");
   if (policy != PP2_CONTROL_MODE && policy != PP2_CONTROL_QMDP)
     return set_err(PP2_EINVAL, "unknown control policy %d", policy);
+  return run_impl(ep, policy, -1, seed, b0, start_cells);
+}
+
+int pp2_episodes_run_alpha(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
+                           const int32_t* start_cells) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (!b0 || !start_cells) return set_err(PP2_EINVAL, "null argument");
+  if (alpha_set != PP2_ALPHA_FIB && alpha_set != PP2_ALPHA_PBVI)
+    return set_err(PP2_EINVAL, "unknown alpha set %d", alpha_set);
+  return run_impl(ep, kPolicyAlpha, alpha_set, seed, b0, start_cells);
+}
+
+int pp2_episodes_trace_alpha(pp2_episodes* ep, int32_t* best_index, float* best_sum) {
+  CHECK(check_ran_alpha(ep, "pp2_episodes_trace_alpha"));
+  if (!ep->trace)
+    return set_err(PP2_ESTATE, "the batch was created without record_trace");
   pp2_ctx* c = ep->ctx;
-  // settles pending resident launches first: J and A below are the current ones
-  long long lds = 0;
-  CHECK(check_episode_ctx(c, ep, &lds));
-  ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
-  const int H = ep->H, W = ep->W, wp = ep->wp, E = ep->episodes;
-  const size_t hw = (size_t)H * W;
-  for (size_t i = 0; i < hw; ++i) {
-    uint32_t bits;
-    std::memcpy(&bits, &b0[i], 4);
-    if (bits >= 0x7f800000u)  // negative (-0 too), infinite or NaN
-      return set_err(PP2_EINVAL, "b0[%zu] is not finite and >= +0", i);
-  }
-  for (int e = 0; e < E; ++e)
-    if (start_cells[e] < 0 || (size_t)start_cells[e] >= hw)
-      return set_err(PP2_EINVAL, "start_cells[%d] = %d outside [0, %zu)", e, start_cells[e], hw);
   DeviceGuard dg(c->device);
-  // the staging vectors may still feed the previous run's copies
+  const size_t HE = (size_t)ep->horizon * ep->episodes;
+  CHECK(fetch(c, best_index, ep->d_trbest, HE));
+  CHECK(fetch(c, best_sum, ep->d_trbsum, HE));
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (int y = 0; y < H; ++y)
-    std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
-  std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
-  const size_t np = (size_t)H * wp, HE = (size_t)ep->horizon * E;
-  HIPCHK(hipMemcpyAsync(ep->d_b0, ep->h_b0.data(), np * sizeof(float), hipMemcpyHostToDevice,
-                        c->stream));
-  HIPCHK(hipMemcpyAsync(ep->d_start, ep->h_start.data(), (size_t)E * sizeof(int32_t),
-                        hipMemcpyHostToDevice, c->stream));
-  if (ep->trace) {
-    // steps not taken: 255, 255, -1, 0, -1
-    HIPCHK(hipMemsetAsync(ep->d_tru, 0xff, HE, c->stream));
-    HIPCHK(hipMemsetAsync(ep->d_trz, 0xff, HE, c->stream));
-    HIPCHK(hipMemsetAsync(ep->d_trcell, 0xff, HE * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(ep->d_trmode, 0xff, HE * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(ep->d_trq, 0, HE * 9 * sizeof(float), c->stream));
-  }
-  HIPCHK(pp2::launch_episode_qplanes(c->stream, c->g, c->d_code, c->d_rows, c->dict_n,
-                                     c->J[c->jcur].v.p, ep->d_q, c->ncus));
-  pp2::EpisodeRun a{};
-  a.g = c->g;
-  a.E = c->dict_n;
-  a.code = c->d_code;
-  a.rows = c->d_rows;
-  a.rfact = c->d_rfact;
-  a.Q = ep->d_q;
-  a.A = c->A;
-  a.b0 = ep->d_b0;
-  a.start = ep->d_start;
-  a.episodes = E;
-  a.horizon = ep->horizon;
-  a.seed = seed;
-  a.gamma = c->gamma;
-  a.goal = c->gy * W + c->gx;
-  a.steps = ep->d_steps;
-  a.status = ep->d_status;
-  a.cost = ep->d_cost;
-  a.final_cell = ep->d_final;
-  a.beliefs = ep->d_beliefs;
-  if (ep->trace) {
-    a.tr_u = ep->d_tru;
-    a.tr_z = ep->d_trz;
-    a.tr_cell = ep->d_trcell;
-    a.tr_q = policy == PP2_CONTROL_QMDP ? ep->d_trq : nullptr;
-    a.tr_mode = ep->d_trmode;
-  }
-  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups));
-  ep->policy = policy;
+  return PP2_OK;
+}
+
+int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t* actions) {
+  CHECK(check_ran_alpha(ep, "pp2_episodes_get_alpha"));
+  if (ep->alpha_k < 1) return set_err(PP2_ESTATE, "the alpha planes were released");
+  pp2_ctx* c = ep->ctx;
+  DeviceGuard dg(c->device);
+  if (count) *count = ep->alpha_k;
+  if (alphas)
+    HIPCHK(hipMemcpy2DAsync(alphas, (size_t)ep->W * sizeof(float), ep->d_alpha,
+                            (size_t)ep->wp * sizeof(float), (size_t)ep->W * sizeof(float),
+                            (size_t)ep->alpha_k * ep->H, hipMemcpyDeviceToHost, c->stream));
+  CHECK(fetch(c, actions, ep->d_alpha_act, (size_t)ep->alpha_k));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return PP2_OK;
 }
 
@@ -274,6 +414,8 @@ int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief) {
 int pp2_episodes_get_q(pp2_episodes* ep, float* Q) {
   CHECK(check_ran(ep, "pp2_episodes_get_q"));
   if (!Q) return set_err(PP2_EINVAL, "Q is null");
+  if (ep->policy == kPolicyAlpha)
+    return set_err(PP2_ESTATE, "an alpha run builds no Q planes");
   pp2_ctx* c = ep->ctx;
   DeviceGuard dg(c->device);
   const size_t np = (size_t)ep->H * ep->wp;

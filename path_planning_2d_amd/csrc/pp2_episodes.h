@@ -16,6 +16,9 @@
 //   code   the code plane, uint16 [H + 2][ps] (off-grid cells and pads: 0)
 //   red    reduction scratch (kEpRedFloats)
 //   b[2]   the belief planes, fp32 [H + 2][ps] + 4
+//   asum   the alpha instance only, K != 9: two buffers of per-wave sums,
+//          [2][kEpAlphaChunk] quads (w0..w3 of a vector) -- on top of the
+//          layout above, which is the MODE and QMDP instances' whole LDS
 // with ps = wp + 4: cell (y, x) of a plane sits at (y + 1) * ps + 4 + x, so
 // x = -1 is the row's last left pad and x = wp the next row's first.
 #pragma once
@@ -26,6 +29,14 @@ namespace pp2 {
 constexpr int kEpThreads = 256;
 constexpr int kEpRedFloats = 48;
 constexpr int kEpMaxPerCu = 8;  // workgroups per CU the grid is sized for
+// The alpha-vector policy (k_episodes<2>): K vectors in blocks of
+// kEpAlphaBlock accumulators, their per-wave sums staged per chunk of
+// kEpAlphaChunk vectors (one barrier per chunk, two buffers).  K = 9 (FIB)
+// takes the QMDP control phase's shape and no scratch.
+constexpr int kEpAlphaBlock = 8;
+constexpr int kEpAlphaChunk = 64;
+constexpr int kEpAlphaMax = 4096;  // PBVI's own limit
+inline __host__ __device__ int ep_alpha_floats(int K) { return K == 9 ? 0 : 2 * kEpAlphaChunk * 4; }
 
 struct EpisodeLds {
   int ps, prows;                         // plane row stride (floats), plane rows
@@ -65,6 +76,11 @@ inline long long episode_lds_bytes(const Geom& g, int E) {
   return 4 * (ep_table_floats(E) + codef + kEpRedFloats + 2 * plane);
 }
 
+// ... of the alpha instance with K vectors
+inline long long episode_alpha_lds_bytes(const Geom& g, int E, int K) {
+  return episode_lds_bytes(g, E) + 4LL * ep_alpha_floats(K);
+}
+
 struct EpisodeRun {
   Geom g;
   int E;                     // dictionary entries
@@ -73,6 +89,9 @@ struct EpisodeRun {
   const float* rfact;        // class tables, then the LX bytes
   const float* Q;            // [9][H][wp], pads +0
   const uint8_t* A;          // [H][wp]
+  const float* alpha;        // alpha runs: [K][H][wp], pads +0
+  const uint8_t* alpha_act;  // [K], every one <= 8
+  int K;
   const float* b0;           // [H][wp], pads +0
   const int32_t* start;      // [episodes], y * W + x
   int episodes, horizon;
@@ -90,13 +109,22 @@ struct EpisodeRun {
   int32_t* tr_cell;
   float* tr_q;               // [horizon][episodes][9]
   int32_t* tr_mode;
+  int32_t* tr_best;          // alpha runs: the winning vector and its sum
+  float* tr_bsum;
 };
 
 // Q[u][y][x] = k_mdp_sweep's cost of action u from J (sparse coded model).
 hipError_t launch_episode_qplanes(hipStream_t st, const Geom& g, const uint16_t* code,
                                   const float* rows, int E, const float* J, float* Q, int ncus);
-// policy: PP2_CONTROL_MODE (0) or PP2_CONTROL_QMDP (1).  hipErrorInvalidValue
-// when the workgroup's LDS does not fit.
+// Alpha planes [K][H][wp], pads +0, from the FIB planes (fib: row stride
+// fib.rs, plane stride fib.ps; K = 9) or from PBVI's flat rows (rows: [K][ld],
+// cell y * W + x); act_out[k] = acts[k], or k without acts (FIB).
+hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const PlaneSet* fib,
+                                       const float* rows, int ld, int K, float* out,
+                                       const uint8_t* acts, uint8_t* act_out);
+// policy: PP2_CONTROL_MODE (0), PP2_CONTROL_QMDP (1) or 2, the alpha-vector
+// policy over a.alpha.  hipErrorInvalidValue when the workgroup's LDS does
+// not fit.
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups);
 
 }  // namespace pp2

@@ -1,5 +1,6 @@
 // pp2_episodes.hip -- batched closed-loop policy episodes on the device
-// (gfx950): k_episode_qplanes writes the nine Q planes of the current J, and
+// (gfx950): k_episode_qplanes writes the nine Q planes of the current J
+// (k_episode_alpha_planes the planes of the FIB / PBVI alpha vectors), and
 // k_episodes runs E independent episodes -- select a control from the belief,
 // move the true robot, sample the observation, update the belief -- each
 // wholly inside one workgroup whose LDS holds the episode's belief
@@ -93,6 +94,37 @@ __global__ __launch_bounds__(kBlock) void k_episode_qplanes(
   }
 }
 
+// ---- alpha planes -----------------------------------------------------------
+// out[k][y][x0 .. x0 + 3] of the alpha policy: the FIB plane k of the row
+// (fib != null) or PBVI's flat row k at y * W + x; pad cells +0.  One thread
+// per quad of one plane.  act_out[k] = acts[k], or k without acts (FIB): the
+// run's snapshot of the actions, without a copy call of its own.
+__global__ __launch_bounds__(kBlock) void k_episode_alpha_planes(
+    Geom g, const float* __restrict__ fib, long long frs, long long fps,
+    const float* __restrict__ rows, int ld, int K, float* __restrict__ out,
+    const uint8_t* __restrict__ acts, uint8_t* __restrict__ act_out) {
+  if (blockIdx.x == 0)
+    for (int k = threadIdx.x; k < K; k += kBlock) act_out[k] = acts ? acts[k] : (uint8_t)k;
+  const int tpr = g.wp / 4;
+  const long long qpp = (long long)g.rows * tpr;  // quads per plane
+  const long long total = qpp * K;
+  for (long long t = (long long)blockIdx.x * kBlock + threadIdx.x; t < total;
+       t += (long long)gridDim.x * kBlock) {
+    const int k = (int)(t / qpp);
+    const long long r = t - (long long)k * qpp;
+    const int y = (int)(r / tpr), x0 = (int)(r % tpr) * 4;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = 0.0f;
+      if (x0 + j < g.width)
+        v[j] = fib ? fib[(long long)y * frs + (long long)k * fps + x0 + j]
+                   : rows[(long long)k * ld + (long long)y * g.width + x0 + j];
+    }
+    store4<false>(out + ((long long)k * g.rows + y) * g.wp + x0, v);
+  }
+}
+
 // ---- random numbers ---------------------------------------------------------
 constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
@@ -151,6 +183,123 @@ __device__ __forceinline__ void mode_take(float& v, int& i, float ov, int oi) {
   for (int I0 = 4 * tid, Y = qy0, X0 = qx0; I0 < NP; I0 += 4 * kEpThreads, Y += qdy, \
            X0 += qdx, Y += X0 >= wp ? 1 : 0, X0 -= X0 >= wp ? wp : 0)
 
+// ---- control of the alpha-vector policy -------------------------------------
+// The lane's partials of NB vectors from k0 on (past K - 1: vector K - 1 again)
+// over one pass of the belief: acc[q] = acc[q] + fl(fl(b * sc) * alpha), the
+// pinned order.  The plane pointers are formed before the pass, so the NB
+// loads of a quad are issued together.
+template <int NB>
+__device__ __forceinline__ void alpha_dots(const EpisodeRun& a, const float* cur, float sc, int k0,
+                                           int tid, int ps, int wp, int NP, int qy0, int qx0,
+                                           int qdy, int qdx, float (&acc)[NB]) {
+  const float* ap[NB];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    acc[q] = 0.0f;
+    ap[q] = a.alpha + (long long)(k0 + q < a.K ? k0 + q : a.K - 1) * NP;
+  }
+  PP2_EP_QUADS(i0, y, x0) {
+    const f4a bv = *reinterpret_cast<const f4a*>(cur + (y + 1) * ps + 4 + x0);
+    float bs[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bs[j] = bv[j] * sc;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const f4a qv = *reinterpret_cast<const f4a*>(ap[q] + i0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float pr = bs[j] * qv[j];
+        acc[q] = acc[q] + pr;
+      }
+    }
+  }
+}
+
+// V_k = <stored belief, alpha_k> in the pinned Q-dot order for k = 0 .. K-1;
+// best = 0, then for k = 1 .. K-1: if (V_best < V_k) best = k (a NaN sum never
+// displaces the incumbent, a NaN V_0 is never displaced).  Returns the action
+// of the winner, workgroup-uniform.
+//  * K = 9 (FIB): the QMDP control phase -- nine accumulators over one pass of
+//    the belief, the per-wave sums in red, one barrier.
+//  * else: blocks of kEpAlphaBlock accumulators, so the belief quads are read
+//    from LDS (and scaled) once per block; the alpha quads are cached 16-byte
+//    loads (every workgroup re-reads the set, from L2).  lane 0 of wave w puts
+//    the wave's sum of vector k at asum[buffer][k - c0][w]; one barrier per
+//    chunk of kEpAlphaChunk vectors, after which every lane folds the chunk's
+//    quads in ascending k.  Two buffers: a wave that writes chunk c + 2 has
+//    passed barrier c + 1, which every wave reaches after its reads of chunk c
+//    (and a step's belief barrier lies between two steps' chunks).  A tail
+//    block re-reads vector K - 1 for its unused accumulators (in bounds, the
+//    sums not stored).
+// The actions of the vectors at hand (all nine; a chunk's 64) are loaded one
+// per lane before the dots and the winner's is read from its lane
+// (v_readlane): no global load of action[best] behind the barrier.
+__device__ __forceinline__ int alpha_control(const EpisodeRun& a, const EpisodeLds& L, float* lds,
+                                             const float* cur, float sc, int k, int e, int qy0,
+                                             int qx0, int qdy, int qdx) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wp = a.g.wp, ps = L.ps, K = a.K;
+  const int NP = a.g.rows * wp;
+  const long long at = (long long)k * a.episodes + e;
+  int best = 0, u = 0;
+  float vbest = 0.0f;
+  if (K == kQ) {
+    float* red = lds + L.red;
+    // lane l holds the action of vector l: loaded ahead of the dots, so the
+    // winner's action is a lane read, not a global load behind the barrier
+    const int av = a.alpha_act[lane < kQ ? lane : kQ - 1];
+    float acc[kQ];
+    alpha_dots<kQ>(a, cur, sc, 0, tid, ps, wp, NP, qy0, qx0, qdy, qdx, acc);
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) {
+      const float v = wave_sum(acc[q]);
+      if (lane == 0) red[wave * kQ + q] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) {
+      const float sq = ((red[q] + red[kQ + q]) + red[2 * kQ + q]) + red[3 * kQ + q];
+      if (q == 0) vbest = sq;
+      else if (vbest < sq) { vbest = sq; best = q; }
+      if (a.tr_q && tid == q) a.tr_q[at * kQ + q] = sq;
+    }
+    u = __builtin_amdgcn_readlane(av, __builtin_amdgcn_readfirstlane(best));
+  } else {
+    float* asum = lds + L.total;
+    for (int c0 = 0, buf = 0; c0 < K; c0 += kEpAlphaChunk, buf ^= 1) {
+      float* as = asum + buf * (kEpAlphaChunk * 4);
+      const int cend = c0 + kEpAlphaChunk < K ? c0 + kEpAlphaChunk : K;
+      // lane l holds the action of vector c0 + l (as above)
+      const int av = a.alpha_act[c0 + lane < K ? c0 + lane : K - 1];
+      for (int kb = c0; kb < cend; kb += kEpAlphaBlock) {
+        float acc[kEpAlphaBlock];
+        alpha_dots<kEpAlphaBlock>(a, cur, sc, kb, tid, ps, wp, NP, qy0, qx0, qdy, qdx, acc);
+#pragma unroll
+        for (int q = 0; q < kEpAlphaBlock; ++q) {
+          const float v = wave_sum(acc[q]);
+          if (lane == 0 && kb + q < cend) as[(kb - c0 + q) * 4 + wave] = v;
+        }
+      }
+      __syncthreads();
+      for (int kk = c0; kk < cend; ++kk) {
+        const f4a w = *reinterpret_cast<const f4a*>(as + (kk - c0) * 4);
+        const float s = ((w[0] + w[1]) + w[2]) + w[3];
+        if (kk == 0) vbest = s;
+        else if (vbest < s) { vbest = s; best = kk; }
+      }
+      best = __builtin_amdgcn_readfirstlane(best);
+      if (best >= c0) u = __builtin_amdgcn_readlane(av, best - c0);
+    }
+  }
+  if (u > 8) u = 8;  // (the run is refused for more; keeps the tables' bounds)
+  if (a.tr_best && tid == 0) {
+    a.tr_best[at] = best;
+    a.tr_bsum[at] = vbest;
+  }
+  return u;
+}
+
+// POLICY: 0 mode, 1 QMDP, 2 the alpha-vector policy (alpha_control).
 template <int POLICY>
 __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -224,6 +373,9 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
     for (int k = 0; k < a.horizon && status == 0; ++k) {
       // 1. control: the lane's partials
       int u = 0, mcell = 0;
+      if constexpr (POLICY == 2) {
+        u = alpha_control(a, L, lds, cur, sc, k, e, qy0, qx0, qdy, qdx);
+      } else {
       if constexpr (POLICY == 1) {
         float acc[kQ];
 #pragma unroll
@@ -283,6 +435,7 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
         mcell = idx == INT_MAX ? 0 : idx;
         u = a.A[(long long)(mcell / W) * wp + mcell % W];
         if (u > 8) u = 8;  // (an action plane never holds more; keeps the tables' bounds)
+      }
       }
       u = __builtin_amdgcn_readfirstlane(u);
 
@@ -428,10 +581,28 @@ hipError_t launch_episode_qplanes(hipStream_t st, const Geom& g, const uint16_t*
   return hipGetLastError();
 }
 
+hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const PlaneSet* fib,
+                                       const float* rows, int ld, int K, float* out,
+                                       const uint8_t* acts, uint8_t* act_out) {
+  if (K < 1 || K > kEpAlphaMax || (!fib && !rows) || (fib && K != 9)) return hipErrorInvalidValue;
+  const long long quads = (long long)g.rows * (g.wp / 4) * K;
+  const long long nblocks = (quads + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_episode_alpha_planes, dim3((unsigned)(nblocks < 4096 ? nblocks : 4096)),
+                     dim3(kBlock), 0, st, g, fib ? fib->p : nullptr, fib ? fib->rs : 0,
+                     fib ? fib->ps : 0, rows, ld, K, out, acts, act_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups) {
-  const long long bytes = episode_lds_bytes(a.g, a.E);
+  const long long bytes =
+      policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K) : episode_lds_bytes(a.g, a.E);
   if (bytes > (long long)kDictLdsMaxBytes || workgroups < 1) return hipErrorInvalidValue;
-  if (policy == 1) {
+  if (policy == 2) {
+    if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<2>), attr);
+    hipLaunchKernelGGL(k_episodes<2>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
+  } else if (policy == 1) {
     static unsigned long long attr = 0;
     allow_lds(reinterpret_cast<const void*>(&k_episodes<1>), attr);
     hipLaunchKernelGGL(k_episodes<1>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);

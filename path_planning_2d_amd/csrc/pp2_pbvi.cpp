@@ -305,6 +305,13 @@ int pbvi_alphas(pp2_ctx* c, const float** alpha, int* S, int* Sp, int* ld) {
   return PP2_OK;
 }
 
+int pbvi_actions(pp2_ctx* c, const uint8_t** actions) {
+  PbviState* p = c->pbvi;
+  if (!p || p->S <= 0) return set_err(PP2_ESTATE, "no PBVI alpha vectors");
+  *actions = p->actions;
+  return PP2_OK;
+}
+
 int pbvi_eval_device(pp2_ctx* c, int n, const float* d_beliefs, int ld, float* d_dots) {
   PbviState* p = c->pbvi;
   HIPCHK(pp2::launch_pair_chain(c->stream, pp2::PAIR_DOT, d_beliefs, n, p->alpha[p->acur], p->S,

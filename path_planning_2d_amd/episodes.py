@@ -1,8 +1,9 @@
 """Batched closed-loop policy episodes (include/pp2.h "episodes").
 
 ``EpisodeBatch`` runs E simulated robots under a control policy -- the
-belief-mode policy of the reference MDP node or the QMDP policy -- each with
-its own belief, for up to ``horizon`` steps in one kernel launch, and returns
+belief-mode policy of the reference MDP node, the QMDP policy, or the greedy
+policy of the FIB alphas or of the PBVI alpha vectors -- each with its own
+belief, for up to ``horizon`` steps in one kernel launch, and returns
 how the policy did: steps to the goal, status and discounted cost per episode.
 Everything runs in libpp2_hip.so; there is no CPU path.
 """
@@ -21,6 +22,10 @@ MAX_HORIZON = 4096
 STATUS_HORIZON = 0   # still running after the last step
 STATUS_GOAL = 1      # the true robot reached the goal
 STATUS_LOST = 2      # the belief update left no finite positive value
+
+ALPHA_FIB = 0        # the context's current FIB alphas (K = 9, action of vector k = k)
+ALPHA_PBVI = 1       # the context's PBVI alpha vectors and their actions (K = S)
+_ALPHA_SETS = {"fib": ALPHA_FIB, "pbvi": ALPHA_PBVI}
 
 
 def _i32(a):
@@ -45,6 +50,7 @@ class EpisodeBatch:
         self.record_trace = bool(record_trace)
         self.cells = ctx.cells
         self.policy = None
+        self.alpha_set = None    # of the last run, if that was an alpha run
         h = C.c_void_p()
         call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
              int(self.record_trace))
@@ -98,11 +104,38 @@ class EpisodeBatch:
 
     def run(self, policy, b0, start_cells, seed: int = 0):
         """Enqueue one batch: every episode starts from belief ``b0`` with its
-        true robot at ``start_cells[e]`` (``y * W + x``).  Asynchronous."""
+        true robot at ``start_cells[e]`` (``y * W + x``).  ``policy``: "mode",
+        "qmdp" (or CONTROL_MODE / CONTROL_QMDP), or "fib" / "pbvi", which are
+        ``run_alpha``.  Asynchronous."""
+        if isinstance(policy, str) and policy in _ALPHA_SETS:
+            return self.run_alpha(policy, b0, start_cells, seed)
         policy, b0, start, seed = self.check_run_args(self.cells, self.episodes, policy, b0,
                                                       start_cells, seed)
         call("pp2_episodes_run", self._h, policy, C.c_uint64(seed), _f32(b0), _i32(start))
         self.policy = policy
+        self.alpha_set = None
+        return self
+
+    def run_alpha(self, alpha_set, b0, start_cells, seed: int = 0):
+        """``run`` under the greedy policy of an alpha-vector set: "fib" (or
+        ALPHA_FIB), the context's current FIB alphas, or "pbvi" (ALPHA_PBVI),
+        its PBVI alpha vectors.  The cost stays the MDP cost, so all four
+        policies are compared on one scale.  Asynchronous."""
+        if isinstance(alpha_set, str):
+            if alpha_set not in _ALPHA_SETS:
+                raise ValueError(f"unknown alpha set {alpha_set!r}")
+            alpha_set = _ALPHA_SETS[alpha_set]
+        if (isinstance(alpha_set, bool) or not isinstance(alpha_set, (int, np.integer))
+                or alpha_set not in (ALPHA_FIB, ALPHA_PBVI)):
+            raise ValueError(f"unknown alpha set {alpha_set!r}")
+        # (b0, the starts and the seed are checked as for any run; the policy
+        # argument only has to be a valid one)
+        _, b0, start, seed = self.check_run_args(self.cells, self.episodes,
+                                                 GridContext.CONTROL_QMDP, b0, start_cells, seed)
+        call("pp2_episodes_run_alpha", self._h, int(alpha_set), C.c_uint64(seed), _f32(b0),
+             _i32(start))
+        self.policy = None
+        self.alpha_set = int(alpha_set)
         return self
 
     def results(self) -> dict:
@@ -117,8 +150,8 @@ class EpisodeBatch:
 
     def trace(self) -> dict:
         """The last run's per-step record, [horizon, E] arrays (qsums
-        [horizon, E, 9]; only for QMDP runs, mode_cells only for mode runs).
-        Steps not taken hold 255, 255, -1, 0, -1."""
+        [horizon, E, 9]: QMDP's S_u or a FIB run's V_k, else 0; mode_cells only
+        for mode runs).  Steps not taken hold 255, 255, -1, 0, -1."""
         sh = (self.horizon, self.episodes)
         a = np.empty(sh, np.uint8)
         z = np.empty(sh, np.uint8)
@@ -127,6 +160,24 @@ class EpisodeBatch:
         mode = np.empty(sh, np.int32)
         call("pp2_episodes_trace", self._h, _u8(a), _u8(z), _i32(cells), _f32(q), _i32(mode))
         return {"actions": a, "observations": z, "cells": cells, "qsums": q, "mode_cells": mode}
+
+    def trace_alpha(self) -> dict:
+        """The last alpha run's winners, [horizon, E]: the index of the winning
+        vector and its sum (steps not taken: -1, 0)."""
+        sh = (self.horizon, self.episodes)
+        best = np.empty(sh, np.int32)
+        vsum = np.empty(sh, np.float32)
+        call("pp2_episodes_trace_alpha", self._h, _i32(best), _f32(vsum))
+        return {"best_index": best, "best_sum": vsum}
+
+    def alphas(self):
+        """(alphas[K, hw], actions[K]): the alpha set the last alpha run read."""
+        k = C.c_int(0)
+        call("pp2_episodes_get_alpha", self._h, C.byref(k), None, None)
+        al = np.empty((k.value, self.cells), np.float32)
+        act = np.empty(k.value, np.uint8)
+        call("pp2_episodes_get_alpha", self._h, C.byref(k), _f32(al), _u8(act))
+        return al, act
 
     def belief(self, e: int) -> np.ndarray:
         """The stored (power-of-two scaled) belief of episode ``e`` after the run."""

@@ -1,14 +1,21 @@
 """Wall time of batched closed-loop policy episodes (pp2_episodes_*, DESIGN.md
 §3.4) on sparse_map_100x40 with the solved J: E = 4096 episodes x horizon 64
-under both policies -- pp2_episodes_run + pp2_episodes_results after a warm-up
-run, median / min / max of 7 rounds, per episode-step and episodes per second
--- against, in alternating rounds of the same process, the host loop the
-library offered before: BeliefMdpController driven by synthetic.closed_loop,
-8 episodes of 64 steps, one belief update and one control call per step.
+under every policy -- mode, QMDP, FIB-greedy (the solved FIB alphas; and
+"fibq", the FIB policy fed -Q, which takes QMDP's very steps, so the two
+kernels are compared on one workload) and PBVI-greedy (pp2_pbvi_solve at every
+--set-size) -- pp2_episodes_run[_alpha] +
+pp2_episodes_results after a warm-up run, median / min / max of 7 rounds, per
+episode-step and episodes per second -- against, in alternating rounds of the
+same process, the host loop the library offered before: BeliefMdpController
+driven by synthetic.closed_loop for mode and QMDP (one belief update and one
+control call per step), and for PBVI one pp2_belief_update, one pp2_belief_get
+and one pp2_pbvi_evaluate per step; 14 episodes of 64 steps each.
 An episode that reaches the goal stops early, so the device's steps are
-counted from the results; the host loop always runs its 64.
+counted from the results; the host loop always runs its 64.  A PBVI entry also
+reports the implied alpha read rate, K * NP * 4 bytes per episode-step.
 
     python tools/episodes_timing.py [--rounds N] [--no-host] [--out FILE]
+                                    [--policies mode,qmdp,fib,fibq,pbvi] [--set-size 21,128,500]
         prints one JSON line (and writes it to FILE)
 
 Kernel time comes from a separate run under
@@ -32,6 +39,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--no-host", action="store_true")
 ap.add_argument("--out", default="")
+ap.add_argument("--policies", default="mode,qmdp,fib,fibq,pbvi")
+ap.add_argument("--set-size", default="21", help="PBVI belief set sizes, comma separated")
 args = ap.parse_args()
 
 E, HORIZON, HOST_EPISODES = 4096, 64, 8
@@ -41,6 +50,13 @@ goal = (95, 34)
 b0 = S.uniform_belief(grid)
 starts = S.sample_cells(b0, E, seed=7)
 out = {"map": "sparse_map_100x40", "episodes": E, "horizon": HORIZON, "rounds": args.rounds}
+policies = [p for p in args.policies.split(",") if p]
+for p in policies:
+    if p not in ("mode", "qmdp", "fib", "fibq", "pbvi"):
+        sys.exit(f"unknown policy {p!r}")
+sizes = [int(s) for s in args.set_size.split(",") if s] if "pbvi" in policies else []
+# the entries timed: a PBVI entry per set size
+entries = [p for p in policies if p != "pbvi"] + [f"pbvi_{s}" for s in sizes]
 
 
 def stats(v, nd=3):
@@ -48,25 +64,66 @@ def stats(v, nd=3):
             "max": round(max(v), nd)}
 
 
+class PbviHostLoop:
+    """The PBVI plan step the library offered before: synchronous calls, the
+    belief through the host."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def step(self, action, observation, belief=None):
+        if belief is not None:
+            self.ctx.belief_set(belief)
+        else:
+            self.ctx.belief_update(action, observation)
+        v, a = self.ctx.pbvi_evaluate(self.ctx.belief_get())
+        return int(a[0]), np.float32(v[0])
+
+
 with P.GridContext(grid, goal, gamma=0.95) as ctx:
     ctx.model_generate()
     out["mdp_sweeps"] = ctx.mdp_solve()[0]
+    fib_sets = {}
+    if "fib" in policies:
+        out["fib_sweeps"] = ctx.fib_solve()[0]
+        fib_sets["fib"] = ctx.fib_get()
+    sets = {}
+    for s in sizes:  # solved once; a round only uploads the set it times
+        ctx.pbvi_solve(b0, s)
+        sets[s] = ctx.pbvi_get()
+    NP = grid.shape[0] * ctx.row_stride
+
+    def prepare(entry):
+        """-> the policy to run"""
+        if entry.startswith("pbvi_"):
+            ctx.pbvi_set(*sets[int(entry[5:])])
+            return "pbvi"
+        if entry in fib_sets:
+            ctx.fib_set(fib_sets[entry])
+            return "fib"
+        return entry
+
     with P.EpisodeBatch(ctx, E, HORIZON) as ep:
         out.update(ep.info())
-        dev = {p: {"wall_ms": [], "steps": 0} for p in ("mode", "qmdp")}
-        host = {p: [] for p in ("mode", "qmdp")}
+        dev = {p: {"wall_ms": [], "steps": 0} for p in entries}
+        host = {p: [] for p in entries}
+        if "fibq" in entries:
+            fib_sets["fibq"] = -ep.run("qmdp", b0, starts, seed=1).qplanes()
         for p in dev:  # warm-up
-            ep.run(p, b0, starts, seed=1).results()
+            ep.run(prepare(p), b0, starts, seed=1).results()
+            dev[p]["info"] = ep.info()
         for rnd in range(args.rounds):  # alternate, so drift hits all alike
             for p in dev:
+                pol = prepare(p)
                 t = time.perf_counter()
-                ep.run(p, b0, starts, seed=1)
+                ep.run(pol, b0, starts, seed=1)
                 res = ep.results()
                 dev[p]["wall_ms"].append((time.perf_counter() - t) * 1e3)
                 dev[p]["steps"] = int(res["steps"].sum())
                 dev[p]["summary"] = ep.summary()
-                if not args.no_host:
-                    ctl = P.BeliefMdpController(ctx, policy=p)
+                if not args.no_host and pol != "fib":
+                    ctl = PbviHostLoop(ctx) if pol == "pbvi" else \
+                        P.BeliefMdpController(ctx, policy=p)
                     t = time.perf_counter()
                     n = 0
                     for h in range(HOST_EPISODES // args.rounds + 1):
@@ -79,7 +136,12 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
             out[p] = {"wall_ms": stats(w), "episode_steps": d["steps"],
                       "us_per_episode_step": stats([x * 1e3 / d["steps"] for x in w], 5),
                       "episodes_per_s": stats([E / (x * 1e-3) for x in w], 0),
-                      "summary": d["summary"]}
+                      "summary": d["summary"], "info": d["info"]}
+            if p.startswith("pbvi_"):
+                nbytes = int(p[5:]) * NP * 4
+                out[p]["alpha_bytes_per_episode_step"] = nbytes
+                out[p]["alpha_read_TB_per_s"] = stats(
+                    [nbytes * d["steps"] / (x * 1e-3) / 1e12 for x in w], 3)
             if host[p]:
                 out[p]["host_loop_us_per_episode_step"] = stats(host[p], 2)
                 out[p]["host_loop_over_device"] = round(
