@@ -1,11 +1,12 @@
 /*
- * pp2_episodes_demo.c -- evaluating the four control policies through the C ABI
+ * pp2_episodes_demo.c -- evaluating the six control policies through the C ABI
  * alone (include/pp2.h "episodes"): solve the MDP, the FIB alphas and a small
  * PBVI set of sparse_map_100x40, then run a batch of simulated closed-loop
  * episodes under the belief-mode policy, the QMDP policy, the FIB-greedy and
- * the PBVI-greedy policy -- the same robots, seed and cost scale, each in one
- * launch -- and print success rate, mean steps to the goal and mean discounted
- * cost.  Plain C99, linked against libpp2_hip.so.
+ * the PBVI-greedy policy and the one-step lookahead over either alpha set --
+ * the same robots, seed and cost scale, each in one launch -- and print success
+ * rate, mean steps to the goal and mean discounted cost.  Plain C99, linked
+ * against libpp2_hip.so.
  *
  *   ./pp2_episodes_demo [map.npy]     (default tests/golden/maps/sparse_map_100x40.npy,
  *                                      from the repository root); exit status 0 on success
@@ -82,14 +83,19 @@ int main(int argc, char** argv) {
   printf("pp2_episodes_demo: MDP solved in %d sweeps, FIB in %d, PBVI with %d beliefs; %d episodes "
          "x %d steps, %d workgroups of %d threads, %d B of LDS each\n", sweeps, fib_sweeps,
          PBVI_SET, EPISODES, HORIZON, wgs, threads, lds);
-  /* mode and QMDP read J and A, the alpha runs the FIB / PBVI vectors */
-  const int policies[4] = {PP2_CONTROL_MODE, PP2_CONTROL_QMDP, PP2_ALPHA_FIB, PP2_ALPHA_PBVI};
-  const char* names[4] = {"mode", "QMDP", "FIB-greedy", "PBVI-greedy"};
-  for (int p = 0; p < 4; ++p) {
+  /* mode and QMDP read J and A, the alpha and the lookahead runs the FIB /
+   * PBVI vectors */
+  const int policies[6] = {PP2_CONTROL_MODE, PP2_CONTROL_QMDP, PP2_ALPHA_FIB,
+                           PP2_ALPHA_PBVI,   PP2_ALPHA_FIB,    PP2_ALPHA_PBVI};
+  const char* names[6] = {"mode", "QMDP", "FIB-greedy", "PBVI-greedy", "FIB-lookahead",
+                          "PBVI-lookahead"};
+  for (int p = 0; p < 6; ++p) {
     if (p < 2)
       CHECK(pp2_episodes_run(ep, policies[p], 2024, b0, start));
-    else
+    else if (p < 4)
       CHECK(pp2_episodes_run_alpha(ep, policies[p], 2024, b0, start));
+    else
+      CHECK(pp2_episodes_run_lookahead(ep, policies[p], 2024, b0, start));
     CHECK(pp2_episodes_results(ep, steps, status, cost, NULL));
     int reached = 0, lost = 0;
     double sum_steps = 0.0, sum_cost = 0.0;

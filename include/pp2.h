@@ -573,7 +573,36 @@ int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
  * A run reads the alpha set that is current when it is enqueued (stream
  * ordered, as J and A): once per run it is repacked into planes [K][row][row
  * stride], pads +0, allocated at the first alpha run and regrown when K grows
- * (PP2_ENOMEM if that fails). */
+ * (PP2_ENOMEM if that fails).
+ *
+ * Lookahead runs (pp2_episodes_run_lookahead): the one-step lookahead policy
+ * over an alpha-vector set -- the reference POMDP node's QV-tree at depth 1
+ * with the exact observation probabilities as weights,
+ *   Q(b, u) = <b, R_u> + gamma * sum_z max_k <L_z . T_u^T b, alpha_k>,
+ * where the unnormalised update carries p(z | b, u) as its mass, so nothing is
+ * divided.  A lookahead run is pp2_episodes_run_alpha with step 1 replaced;
+ * steps 2-6, the random numbers, the results, the statuses and the MDP cost
+ * scale are unchanged.  b is the stored belief, dot the pinned Q-dot order
+ * above (separate roundings, flush-to-zero, padded planes, pads +0), gamma the
+ * context's, and the alpha set (K vectors and their actions) is read and
+ * repacked once per run exactly as an alpha run does.
+ *  1. control.  For u = 0..8:
+ *       rew[u] = dot(b, Rp_u), Rp_u[y*stride + x] = R[y*W + x][u], the POMDP
+ *         stage reward of pp2_model_download, pads +0 (repacked once per run
+ *         from the context's R planes, as the Q planes are);
+ *       for z = 0..15: raw_uz = step 5's unnormalised update of b by (u, z)
+ *         (the fmaf chain, then * L_z, flush-to-zero; cells x >= W and pads
+ *         +0) -- the bits step 5 stores when (u, z) is the pair that happens;
+ *         V_uzk = dot(raw_uz, alpha_k) for k = 0..K-1; i_uz = 0, then for
+ *         k = 1..K-1: if (V[i_uz] < V[k]) i_uz = k (the alpha run's rule: the
+ *         first maximum wins, NaN never displaces the incumbent);
+ *         M_uz = V[i_uz];
+ *       S_u = +0, then z ascending: S_u = S_u + M_uz;
+ *       Q_u = rew[u] + fl(gamma * S_u) (separate roundings, no fmaf).
+ *     best = 0, then for u = 1..8: if (Q_best < Q_u) best = u; the control is
+ *     best itself.  The vectors' own actions do not enter the choice (they are
+ *     still validated <= 8).  Non-finite alpha entries are not rejected: the
+ *     arithmetic above is the definition. */
 typedef struct pp2_episodes pp2_episodes;
 /* episodes 1..131072, horizon 1..4096; record_trace != 0 keeps the per-step
  * trace.  PP2_ESTATE: no model, a row shard or group member, coded model
@@ -604,7 +633,7 @@ int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief);
 int pp2_episodes_get_q(pp2_episodes* ep, float* Q);
 /* LDS bytes per workgroup, workgroups and threads per workgroup of the last
  * launch (before any run: of a MODE / QMDP launch; an alpha launch adds its
- * scratch for K != 9) */
+ * scratch for K != 9, a lookahead launch its own) */
 int pp2_episodes_info(pp2_episodes* ep, int* lds_bytes, int* workgroups, int* threads);
 #define PP2_ALPHA_FIB  0   /* the context's current FIB alphas: K = 9, action of vector k = k */
 #define PP2_ALPHA_PBVI 1   /* the context's PBVI alpha vectors and their actions: K = S */
@@ -621,9 +650,28 @@ int pp2_episodes_run_alpha(pp2_episodes* ep, int alpha_set, uint64_t seed, const
  * sum; steps not taken: -1, 0.  PP2_ESTATE unless the last run was an alpha
  * run, or without record_trace. */
 int pp2_episodes_trace_alpha(pp2_episodes* ep, int32_t* best_index, float* best_sum);
-/* the alpha set the last alpha run read: *count = K; alphas [K][hw], actions
- * [K]; any may be NULL.  PP2_ESTATE unless the last run was an alpha run. */
+/* the alpha set the last alpha or lookahead run read: *count = K; alphas
+ * [K][hw], actions [K]; any may be NULL.  PP2_ESTATE unless the last run was
+ * an alpha or a lookahead run. */
 int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t* actions);
+/* pp2_episodes_run with the one-step lookahead policy over an alpha set
+ * ("Lookahead runs" above): arguments, checks, statuses and asynchrony are
+ * those of pp2_episodes_run_alpha; PP2_EINVAL before any launch also when the
+ * workgroup's LDS with the lookahead scratch does not fit.  Afterwards
+ * pp2_episodes_trace returns actions, observations and cells as usual, qsums =
+ * the nine Q_u and mode_cells = -1; pp2_episodes_get_alpha answers with the
+ * set read; pp2_episodes_trace_alpha and pp2_episodes_get_q return PP2_ESTATE;
+ * pp2_episodes_info reports the lookahead launch (its scratch added). */
+int pp2_episodes_run_lookahead(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
+                               const int32_t* start_cells);
+/* The last lookahead run's trace, any may be NULL: q and rewards
+ * [horizon][episodes][9] (Q_u, rew[u]); leaf_max and leaf_index
+ * [horizon][episodes][9][16] (M_uz, i_uz).  Steps not taken hold 0, 0, 0, -1.
+ * PP2_ESTATE unless the last run was a lookahead run with record_trace.  The
+ * two large arrays are allocated at the first lookahead run of a tracing batch
+ * (PP2_ENOMEM if that fails), never at create. */
+int pp2_episodes_trace_lookahead(pp2_episodes* ep, float* q, float* rewards, float* leaf_max,
+                                 int32_t* leaf_index);
 
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):

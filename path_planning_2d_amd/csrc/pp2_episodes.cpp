@@ -1,7 +1,8 @@
 // pp2_episodes.cpp -- C ABI of the batched closed-loop policy episodes
 // (include/pp2.h "episodes").  Kernels: pp2_episodes.hip.  A run enqueues the
 // Q planes of the current J -- an alpha run the planes of the current FIB or
-// PBVI alpha vectors instead -- and one launch of the persistent episode kernel
+// PBVI alpha vectors instead, a lookahead run those and the reward planes --
+// and one launch of the persistent episode kernel
 // on the context's stream; results, traces and beliefs are copied back on demand.
 #include <cstring>
 #include <vector>
@@ -16,8 +17,8 @@ struct pp2_episodes {
   int episodes = 0, horizon = 0;
   bool trace = false;
   int H = 0, W = 0, wp = 0;    // the geometry the buffers were sized for
-  int policy = -1;             // of the last run (-1: none yet; 2: an alpha run)
-  int alpha_set = -1;          // of the last run, if that was an alpha run
+  int policy = -1;             // of the last run (-1: none yet; 2: an alpha run; 3: a lookahead run)
+  int alpha_set = -1;          // of the last run, if that was an alpha or a lookahead run
   int lds_bytes = 0, workgroups = 0;  // of the last launch (before any: MODE / QMDP's)
   int base_workgroups = 0;     // of a MODE / QMDP launch
   float* d_alpha = nullptr;    // [alpha_cap][H][wp], from the first alpha run on
@@ -25,6 +26,10 @@ struct pp2_episodes {
   int alpha_cap = 0, alpha_k = 0;  // vectors allocated, vectors of the last alpha run
   int32_t* d_trbest = nullptr;  // alpha traces, [horizon][E]
   float* d_trbsum = nullptr;
+  float* d_rplanes = nullptr;  // [9][H][wp] reward planes, from the first lookahead run on
+  float* d_larew = nullptr;    // lookahead traces: [horizon][E][9],
+  float* d_lamax = nullptr;    // [horizon][E][9][16]
+  int32_t* d_laidx = nullptr;
   unsigned acts_ok_version = 0;  // the context's pbvi_version whose actions were found <= 8
   float* d_q = nullptr;        // [9][H][wp]
   float* d_b0 = nullptr;       // [H][wp]
@@ -88,7 +93,11 @@ int fetch(pp2_ctx* c, T* dst, const T* src, size_t n) {
   return PP2_OK;
 }
 
-constexpr int kPolicyAlpha = 2;  // launch_episodes' alpha-vector instance
+constexpr int kPolicyAlpha = 2;      // launch_episodes' alpha-vector instance
+constexpr int kPolicyLookahead = 3;  // ... and its one-step lookahead instance
+// a lookahead workgroup's waves hold two to a SIMD (registers), so two
+// workgroups to a CU
+constexpr int kLookaheadPerCu = 2;
 
 int check_ran_alpha(const pp2_episodes* ep, const char* fn) {
   if (!ep) return set_err(PP2_EINVAL, "null episode batch");
@@ -97,20 +106,31 @@ int check_ran_alpha(const pp2_episodes* ep, const char* fn) {
   return PP2_OK;
 }
 
+// pp2_episodes_get_alpha: the set of an alpha or a lookahead run
+int check_ran_alpha_set(const pp2_episodes* ep, const char* fn) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (ep->policy != kPolicyAlpha && ep->policy != kPolicyLookahead)
+    return set_err(PP2_ESTATE, "%s: the last run read no alpha set", fn);
+  return PP2_OK;
+}
+
 // persistent workgroups: as many as the CUs hold at once, at most one per episode
-int episode_workgroups(const pp2_ctx* c, int episodes, long long lds) {
+int episode_workgroups(const pp2_ctx* c, int episodes, long long lds,
+                       int max_per_cu = pp2::kEpMaxPerCu) {
   int per_cu = (int)((long long)pp2::kDictLdsMaxBytes / lds);
-  per_cu = per_cu < 1 ? 1 : per_cu > pp2::kEpMaxPerCu ? pp2::kEpMaxPerCu : per_cu;
+  per_cu = per_cu < 1 ? 1 : per_cu > max_per_cu ? max_per_cu : per_cu;
   const long long cap = (long long)(c->ncus > 0 ? c->ncus : 256) * per_cu;
   return (int)(episodes < cap ? episodes : cap);
 }
 
-// One run.  policy: PP2_CONTROL_MODE / PP2_CONTROL_QMDP, or kPolicyAlpha with
-// alpha_set PP2_ALPHA_FIB / PP2_ALPHA_PBVI (all checked by the callers).
+// One run.  policy: PP2_CONTROL_MODE / PP2_CONTROL_QMDP, or kPolicyAlpha /
+// kPolicyLookahead with alpha_set PP2_ALPHA_FIB / PP2_ALPHA_PBVI (all checked
+// by the callers).
 int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const float* b0,
              const int32_t* start_cells) {
   pp2_ctx* c = ep->ctx;
-  const bool alpha = policy == kPolicyAlpha;
+  const bool look = policy == kPolicyLookahead;
+  const bool alpha = policy == kPolicyAlpha || look;  // reads an alpha set
   // settles pending resident launches first: J and A below are the current ones
   long long lds = 0;
   CHECK(check_episode_ctx(c, ep, &lds));
@@ -130,12 +150,13 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
       if (K > pp2::kEpAlphaMax)
         return set_err(PP2_EINVAL, "%d alpha vectors (at most %d)", K, pp2::kEpAlphaMax);
     }
-    lds = pp2::episode_alpha_lds_bytes(c->g, c->dict_n, K);
+    lds = look ? pp2::episode_lookahead_lds_bytes(c->g, c->dict_n)
+               : pp2::episode_alpha_lds_bytes(c->g, c->dict_n, K);
     if (lds > (long long)pp2::kDictLdsMaxBytes)
       return set_err(PP2_EINVAL,
-                     "a %d x %d belief with the alpha scratch needs %lld bytes of LDS per "
+                     "a %d x %d belief with the %s scratch needs %lld bytes of LDS per "
                      "episode (at most %zu fit)",
-                     W, H, lds, pp2::kDictLdsMaxBytes);
+                     W, H, look ? "lookahead" : "alpha", lds, pp2::kDictLdsMaxBytes);
   }
   for (size_t i = 0; i < hw; ++i) {
     uint32_t bits;
@@ -173,11 +194,20 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
       CHECK(dev_alloc(&ep->d_alpha_act, (size_t)K, "alpha actions"));
       ep->alpha_cap = K;
     }
-    if (ep->trace && !ep->d_trbest) CHECK(dev_alloc(&ep->d_trbest, HE, "winner trace"));
-    if (ep->trace && !ep->d_trbsum) CHECK(dev_alloc(&ep->d_trbsum, HE, "winning-sum trace"));
+    if (!look) {
+      if (ep->trace && !ep->d_trbest) CHECK(dev_alloc(&ep->d_trbest, HE, "winner trace"));
+      if (ep->trace && !ep->d_trbsum) CHECK(dev_alloc(&ep->d_trbsum, HE, "winning-sum trace"));
+    } else {
+      if (!ep->d_rplanes) CHECK(dev_alloc(&ep->d_rplanes, 9 * np, "reward planes"));
+      if (ep->trace && !ep->d_larew) CHECK(dev_alloc(&ep->d_larew, HE * 9, "reward trace"));
+      if (ep->trace && !ep->d_lamax) CHECK(dev_alloc(&ep->d_lamax, HE * 144, "leaf-maximum trace"));
+      if (ep->trace && !ep->d_laidx) CHECK(dev_alloc(&ep->d_laidx, HE * 144, "leaf-index trace"));
+    }
   }
   ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
-  ep->workgroups = alpha ? episode_workgroups(c, E, lds) : ep->base_workgroups;
+  ep->workgroups = look    ? episode_workgroups(c, E, lds, kLookaheadPerCu)
+                   : alpha ? episode_workgroups(c, E, lds)
+                           : ep->base_workgroups;
   for (int y = 0; y < H; ++y)
     std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
   std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
@@ -192,7 +222,11 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     HIPCHK(hipMemsetAsync(ep->d_trcell, 0xff, HE * sizeof(int32_t), c->stream));
     HIPCHK(hipMemsetAsync(ep->d_trmode, 0xff, HE * sizeof(int32_t), c->stream));
     HIPCHK(hipMemsetAsync(ep->d_trq, 0, HE * 9 * sizeof(float), c->stream));
-    if (alpha) {
+    if (look) {
+      HIPCHK(hipMemsetAsync(ep->d_larew, 0, HE * 9 * sizeof(float), c->stream));
+      HIPCHK(hipMemsetAsync(ep->d_lamax, 0, HE * 144 * sizeof(float), c->stream));
+      HIPCHK(hipMemsetAsync(ep->d_laidx, 0xff, HE * 144 * sizeof(int32_t), c->stream));
+    } else if (alpha) {
       HIPCHK(hipMemsetAsync(ep->d_trbest, 0xff, HE * sizeof(int32_t), c->stream));
       HIPCHK(hipMemsetAsync(ep->d_trbsum, 0, HE * sizeof(float), c->stream));
     }
@@ -202,6 +236,10 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     const bool fib = alpha_set == PP2_ALPHA_FIB;
     HIPCHK(pp2::launch_episode_alpha_planes(c->stream, c->g, fib ? &c->fib[c->fcur].v : nullptr,
                                             d_rows, ld, K, ep->d_alpha, d_acts, ep->d_alpha_act));
+    // ... and of the POMDP stage rewards, R_u[y][x] as nine planes
+    if (look)
+      HIPCHK(pp2::launch_episode_alpha_planes(c->stream, c->g, &c->R.v, nullptr, 0, 9,
+                                              ep->d_rplanes, nullptr, nullptr));
   } else {
     HIPCHK(pp2::launch_episode_qplanes(c->stream, c->g, c->d_code, c->d_rows, c->dict_n,
                                        c->J[c->jcur].v.p, ep->d_q, c->ncus));
@@ -218,6 +256,7 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     a.alpha = ep->d_alpha;
     a.alpha_act = ep->d_alpha_act;
     a.K = K;
+    a.rplanes = look ? ep->d_rplanes : nullptr;
   }
   a.b0 = ep->d_b0;
   a.start = ep->d_start;
@@ -235,11 +274,16 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     a.tr_u = ep->d_tru;
     a.tr_z = ep->d_trz;
     a.tr_cell = ep->d_trcell;
-    // the nine sums: QMDP's S_u, a FIB run's V_k
-    a.tr_q = policy == PP2_CONTROL_QMDP || (alpha && alpha_set == PP2_ALPHA_FIB) ? ep->d_trq
-                                                                                 : nullptr;
+    // the nine sums: QMDP's S_u, a FIB run's V_k, a lookahead run's Q_u
+    a.tr_q = policy == PP2_CONTROL_QMDP || look || (alpha && alpha_set == PP2_ALPHA_FIB)
+                 ? ep->d_trq
+                 : nullptr;
     a.tr_mode = ep->d_trmode;
-    if (alpha) {
+    if (look) {
+      a.tr_rew = ep->d_larew;
+      a.tr_lmax = ep->d_lamax;
+      a.tr_lidx = ep->d_laidx;
+    } else if (alpha) {
       a.tr_best = ep->d_trbest;
       a.tr_bsum = ep->d_trbsum;
     }
@@ -263,7 +307,9 @@ int pp2_episodes_destroy(pp2_episodes* ep) {
                   (void*)ep->d_final, (void*)ep->d_cost, (void*)ep->d_status,
                   (void*)ep->d_beliefs, (void*)ep->d_tru, (void*)ep->d_trz, (void*)ep->d_trcell,
                   (void*)ep->d_trmode, (void*)ep->d_trq, (void*)ep->d_alpha,
-                  (void*)ep->d_alpha_act, (void*)ep->d_trbest, (void*)ep->d_trbsum})
+                  (void*)ep->d_alpha_act, (void*)ep->d_trbest, (void*)ep->d_trbsum,
+                  (void*)ep->d_rplanes, (void*)ep->d_larew, (void*)ep->d_lamax,
+                  (void*)ep->d_laidx})
     if (p) (void)hipFree(p);
   delete ep;
   return PP2_OK;
@@ -337,6 +383,33 @@ int pp2_episodes_run_alpha(pp2_episodes* ep, int alpha_set, uint64_t seed, const
   return run_impl(ep, kPolicyAlpha, alpha_set, seed, b0, start_cells);
 }
 
+int pp2_episodes_run_lookahead(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
+                               const int32_t* start_cells) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (!b0 || !start_cells) return set_err(PP2_EINVAL, "null argument");
+  if (alpha_set != PP2_ALPHA_FIB && alpha_set != PP2_ALPHA_PBVI)
+    return set_err(PP2_EINVAL, "unknown alpha set %d", alpha_set);
+  return run_impl(ep, kPolicyLookahead, alpha_set, seed, b0, start_cells);
+}
+
+int pp2_episodes_trace_lookahead(pp2_episodes* ep, float* q, float* rewards, float* leaf_max,
+                                 int32_t* leaf_index) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (ep->policy != kPolicyLookahead)
+    return set_err(PP2_ESTATE, "pp2_episodes_trace_lookahead: the last run was not a lookahead run");
+  if (!ep->trace)
+    return set_err(PP2_ESTATE, "the batch was created without record_trace");
+  pp2_ctx* c = ep->ctx;
+  DeviceGuard dg(c->device);
+  const size_t HE = (size_t)ep->horizon * ep->episodes;
+  CHECK(fetch(c, q, ep->d_trq, HE * 9));
+  CHECK(fetch(c, rewards, ep->d_larew, HE * 9));
+  CHECK(fetch(c, leaf_max, ep->d_lamax, HE * 144));
+  CHECK(fetch(c, leaf_index, ep->d_laidx, HE * 144));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PP2_OK;
+}
+
 int pp2_episodes_trace_alpha(pp2_episodes* ep, int32_t* best_index, float* best_sum) {
   CHECK(check_ran_alpha(ep, "pp2_episodes_trace_alpha"));
   if (!ep->trace)
@@ -351,7 +424,7 @@ int pp2_episodes_trace_alpha(pp2_episodes* ep, int32_t* best_index, float* best_
 }
 
 int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t* actions) {
-  CHECK(check_ran_alpha(ep, "pp2_episodes_get_alpha"));
+  CHECK(check_ran_alpha_set(ep, "pp2_episodes_get_alpha"));
   if (ep->alpha_k < 1) return set_err(PP2_ESTATE, "the alpha planes were released");
   pp2_ctx* c = ep->ctx;
   DeviceGuard dg(c->device);
@@ -414,8 +487,8 @@ int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief) {
 int pp2_episodes_get_q(pp2_episodes* ep, float* Q) {
   CHECK(check_ran(ep, "pp2_episodes_get_q"));
   if (!Q) return set_err(PP2_EINVAL, "Q is null");
-  if (ep->policy == kPolicyAlpha)
-    return set_err(PP2_ESTATE, "an alpha run builds no Q planes");
+  if (ep->policy == kPolicyAlpha || ep->policy == kPolicyLookahead)
+    return set_err(PP2_ESTATE, "an alpha or a lookahead run builds no Q planes");
   pp2_ctx* c = ep->ctx;
   DeviceGuard dg(c->device);
   const size_t np = (size_t)ep->H * ep->wp;

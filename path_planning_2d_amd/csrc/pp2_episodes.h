@@ -19,6 +19,9 @@
 //   asum   the alpha instance only, K != 9: two buffers of per-wave sums,
 //          [2][kEpAlphaChunk] quads (w0..w3 of a vector) -- on top of the
 //          layout above, which is the MODE and QMDP instances' whole LDS
+//   sums   the lookahead instance only, in asum's place: two buffers of
+//          per-wave sums, [2][16 z x kLaK vectors] quads (w0..w3 of a pair),
+//   ltt    ... then the L columns transposed, [kResLK classes][16 z]
 // with ps = wp + 4: cell (y, x) of a plane sits at (y + 1) * ps + 4 + x, so
 // x = -1 is the row's last left pad and x = wp the next row's first.
 #pragma once
@@ -37,6 +40,14 @@ constexpr int kEpAlphaBlock = 8;
 constexpr int kEpAlphaChunk = 64;
 constexpr int kEpAlphaMax = 4096;  // PBVI's own limit
 inline __host__ __device__ int ep_alpha_floats(int K) { return K == 9 ? 0 : 2 * kEpAlphaChunk * 4; }
+
+// The one-step lookahead policy (k_episodes<3>): per action, blocks of
+// kLaZ x kLaK (observation, vector) accumulators, their per-wave sums staged
+// per block (one barrier per block, two buffers).
+constexpr int kLaZ = 16;
+constexpr int kLaK = 4;
+constexpr int kLaSums = kLaZ * kLaK * 4;  // floats of one buffer
+inline __host__ __device__ int ep_lookahead_floats() { return 2 * kLaSums + kLaZ * kResLK; }
 
 struct EpisodeLds {
   int ps, prows;                         // plane row stride (floats), plane rows
@@ -81,6 +92,11 @@ inline long long episode_alpha_lds_bytes(const Geom& g, int E, int K) {
   return episode_lds_bytes(g, E) + 4LL * ep_alpha_floats(K);
 }
 
+// ... of the lookahead instance
+inline long long episode_lookahead_lds_bytes(const Geom& g, int E) {
+  return episode_lds_bytes(g, E) + 4LL * ep_lookahead_floats();
+}
+
 struct EpisodeRun {
   Geom g;
   int E;                     // dictionary entries
@@ -111,6 +127,11 @@ struct EpisodeRun {
   int32_t* tr_mode;
   int32_t* tr_best;          // alpha runs: the winning vector and its sum
   float* tr_bsum;
+  // lookahead runs: the POMDP reward planes [9][H][wp], pads +0, and the trace
+  const float* rplanes;
+  float* tr_rew;             // [horizon][episodes][9]
+  float* tr_lmax;            // [horizon][episodes][9][16]
+  int32_t* tr_lidx;
 };
 
 // Q[u][y][x] = k_mdp_sweep's cost of action u from J (sparse coded model).
@@ -118,13 +139,14 @@ hipError_t launch_episode_qplanes(hipStream_t st, const Geom& g, const uint16_t*
                                   const float* rows, int E, const float* J, float* Q, int ncus);
 // Alpha planes [K][H][wp], pads +0, from the FIB planes (fib: row stride
 // fib.rs, plane stride fib.ps; K = 9) or from PBVI's flat rows (rows: [K][ld],
-// cell y * W + x); act_out[k] = acts[k], or k without acts (FIB).
+// cell y * W + x); act_out[k] = acts[k], or k without acts (FIB); act_out may
+// be null (the reward planes of a lookahead run: fib = the R plane set).
 hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const PlaneSet* fib,
                                        const float* rows, int ld, int K, float* out,
                                        const uint8_t* acts, uint8_t* act_out);
-// policy: PP2_CONTROL_MODE (0), PP2_CONTROL_QMDP (1) or 2, the alpha-vector
-// policy over a.alpha.  hipErrorInvalidValue when the workgroup's LDS does
-// not fit.
+// policy: PP2_CONTROL_MODE (0), PP2_CONTROL_QMDP (1), 2, the alpha-vector
+// policy over a.alpha, or 3, the one-step lookahead over a.alpha and
+// a.rplanes.  hipErrorInvalidValue when the workgroup's LDS does not fit.
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups);
 
 }  // namespace pp2

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_episode_alpha_planes(
     Geom g, const float* __restrict__ fib, long long frs, long long fps,
     const float* __restrict__ rows, int ld, int K, float* __restrict__ out,
     const uint8_t* __restrict__ acts, uint8_t* __restrict__ act_out) {
-  if (blockIdx.x == 0)
+  if (blockIdx.x == 0 && act_out)
     for (int k = threadIdx.x; k < K; k += kBlock) act_out[k] = acts ? acts[k] : (uint8_t)k;
   const int tpr = g.wp / 4;
   const long long qpp = (long long)g.rows * tpr;  // quads per plane
@@ -299,7 +299,228 @@ __device__ __forceinline__ int alpha_control(const EpisodeRun& a, const EpisodeL
   return u;
 }
 
-// POLICY: 0 mode, 1 QMDP, 2 the alpha-vector policy (alpha_control).
+// ---- control of the one-step lookahead policy -------------------------------
+// 64 per-lane values summed across the wave as a reduce-scatter
+// (wave_sum_scatter128's scheme, pp2_device.h): every butterfly stage (xor 32,
+// 16, 8, 4, 2, 1) halves the values a lane carries, and lane l ends with the
+// total of value l -- each total is v_i + v_{i^m} stage by stage from 32 down,
+// wave_sum's association, bit for bit.
+__device__ __forceinline__ float wave_sum_scatter64(const float (&v)[64]) {
+  const int lane = threadIdx.x & 63;
+  float v1[32], v2[16], v3[8], v4[4], v5[2], v6[1];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[j]),
+                                                    __float_as_uint(v[32 + j]), false, false);
+    v1[j] = __uint_as_float(h[0]) + __uint_as_float(h[1]);
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const auto h = __builtin_amdgcn_permlane16_swap(__float_as_uint(v1[j]),
+                                                    __float_as_uint(v1[16 + j]), false, false);
+    v2[j] = __uint_as_float(h[0]) + __uint_as_float(h[1]);
+  }
+  auto x8 = [](float x) {
+    const float m = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, false));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x141, 0xf, 0xf, false));
+  };
+  auto x4 = [](float x) {
+    const float m = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, false));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x1b, 0xf, 0xf, false));
+  };
+  auto x2 = [](float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4e, 0xf, 0xf, false));
+  };
+  auto x1 = [](float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xb1, 0xf, 0xf, false));
+  };
+  // keep the half this lane's xor-group owns, add the partner's copy of it
+#define PP2_HALVE(SRC, DST, N, D, XF)                                  \
+  {                                                                    \
+    const bool h_ = lane & (D);                                        \
+    _Pragma("unroll") for (int j = 0; j < (N); ++j) {                  \
+      const float keep = h_ ? SRC[(N) + j] : SRC[j];                   \
+      const float send = h_ ? SRC[j] : SRC[(N) + j];                   \
+      DST[j] = keep + XF(send);                                        \
+    }                                                                  \
+  }
+  PP2_HALVE(v2, v3, 8, 8, x8)
+  PP2_HALVE(v3, v4, 4, 4, x4)
+  PP2_HALVE(v4, v5, 2, 2, x2)
+  PP2_HALVE(v5, v6, 1, 1, x1)
+#undef PP2_HALVE
+  return v6[0];
+}
+
+// One block of the lookahead dots: the lane's partials of the 16 z x NK pairs
+// (z, vector kb + q) over one pass of pred = the gather of the stored belief
+// for the action at hand, x >= W zeroed: raw_z = fl(pred * L_z) (step 5's
+// bits), acc[z][q] = acc[z][q] + fl(raw_z * alpha), the pinned order.  A cell's
+// sixteen L_z are four 16-byte reads of the transposed table ltt through its L
+// class (the LX byte is 4 * class, so 4 * LX floats in); the pred quad, the
+// codes and each alpha quad are read once.  v[4 z + q] = acc[z][q] (q >= NK: 0).
+template <int NK>
+__device__ __forceinline__ void lookahead_block(const EpisodeRun& a, const float* pred,
+                                                const uint16_t* sCode, const uint8_t* sLX,
+                                                const float* ltt, int kb, int tid, int ps, int wp,
+                                                int NP, int qy0, int qx0, int qdy, int qdx,
+                                                float (&v)[64]) {
+  float acc[kLaZ][NK];
+  const float* ap[NK];
+#pragma unroll
+  for (int q = 0; q < NK; ++q) ap[q] = a.alpha + (long long)(kb + q) * NP;
+#pragma unroll
+  for (int z = 0; z < kLaZ; ++z)
+#pragma unroll
+    for (int q = 0; q < NK; ++q) acc[z][q] = 0.0f;
+  PP2_EP_QUADS(i0, y, x0) {
+    const int at = (y + 1) * ps + 4 + x0;
+    const f4a pv = *reinterpret_cast<const f4a*>(pred + at);
+    const uint2 cm = *reinterpret_cast<const uint2*>(sCode + at);
+    const uint32_t cc[4] = {cm.x & 0xffffu, cm.x >> 16, cm.y & 0xffffu, cm.y >> 16};
+    f4a av[NK];
+#pragma unroll
+    for (int q = 0; q < NK; ++q) av[q] = *reinterpret_cast<const f4a*>(ap[q] + i0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float* lc = ltt + 4 * sLX[cc[j]];
+#pragma unroll
+      for (int zq = 0; zq < kLaZ / 4; ++zq) {
+        const f4a lv = *reinterpret_cast<const f4a*>(lc + 4 * zq);
+#pragma unroll
+        for (int zj = 0; zj < 4; ++zj) {
+          const float raw = pv[j] * lv[zj];
+#pragma unroll
+          for (int q = 0; q < NK; ++q) {
+            const float pr = raw * av[q][j];
+            acc[4 * zq + zj][q] = acc[4 * zq + zj][q] + pr;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int z = 0; z < kLaZ; ++z)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[4 * z + q] = q < NK ? acc[z][q < NK ? q : 0] : 0.0f;
+}
+
+// Q_u = <b, R_u> + fl(gamma * sum_z max_k <raw_uz, alpha_k>) for u = 0 .. 8
+// (include/pp2.h "Lookahead runs"); returns the first maximum, workgroup-uniform.
+// Per action:
+//  * one gather of the stored belief (step 5's window and fmaf chain, before
+//    * L_z) into the idle plane `pred` -- 9 gathers a step, not 144 -- with the
+//    lane's partial of rew[u] on the way; a lane reads back only the quads it
+//    wrote, so no barrier lies between the gather and the dots, and only cells
+//    that step 5 overwrites are written (halo rows and x pads stay zero);
+//  * blocks of 16 z x 4 k accumulators over pred (lookahead_block; a tail
+//    block carries only its live vectors), folded per wave by
+//    wave_sum_scatter64: lane 4 z + q of wave w puts its total at
+//    sums[buffer][4 z + q][w]; one barrier per block, after which lane l folds
+//    the quads of z = l % 16 in ascending k into its running (max, index).
+//    Two buffers, as alpha_control's chunks.
+//  * S_u from the sixteen lanes' maxima in ascending z (lane reads).
+__device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const EpisodeLds& L,
+                                                 float* lds, const float* cur, float* pred,
+                                                 float sc, int k, int e, int qy0, int qx0,
+                                                 int qdy, int qdx) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int W = a.g.width, wp = a.g.wp, ps = L.ps, K = a.K;
+  const int NP = a.g.rows * wp;
+  const long long at = (long long)k * a.episodes + e;
+  float* red = lds + L.red;
+  float* sums = lds + L.total;
+  const float* ltt = sums + 2 * kLaSums;
+  const float* sRf = lds + L.rf;
+  const uint8_t* sCls = reinterpret_cast<const uint8_t*>(lds + L.cls);
+  const uint16_t* sCode = reinterpret_cast<const uint16_t*>(lds + L.code);
+  const uint8_t* sLX = reinterpret_cast<const uint8_t*>(sRf + kResLX);
+  const float* sQR = sRf + kResQR;
+  int best = 0, buf = 0;
+  float qbest = 0.0f;
+  for (int u = 0; u < kQ; ++u) {
+    const uint8_t* cu = sCls + u * L.epad;
+    const float* qru = sQR + u * kFactK * 4;
+    const float* rp = a.rplanes + (long long)u * NP;
+    float accr = 0.0f;
+    PP2_EP_QUADS(i0, y, x0) {
+      float win[3][6];
+      uint32_t cw[3][6];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int wa = (y + r) * ps + 4 + x0;
+        const f4a mid = *reinterpret_cast<const f4a*>(cur + wa);
+        win[r][0] = cur[wa - 1] * sc;
+        win[r][1] = mid[0] * sc; win[r][2] = mid[1] * sc;
+        win[r][3] = mid[2] * sc; win[r][4] = mid[3] * sc;
+        win[r][5] = cur[wa + 4] * sc;
+        const uint2 cm = *reinterpret_cast<const uint2*>(sCode + wa);
+        cw[r][0] = sCode[wa - 1];
+        cw[r][1] = cm.x & 0xffffu; cw[r][2] = cm.x >> 16;
+        cw[r][3] = cm.y & 0xffffu; cw[r][4] = cm.y >> 16;
+        cw[r][5] = sCode[wa + 4];
+      }
+      float p[4];
+      ep_gather_any(u, cu, qru, cw, win, p);
+      const f4a rv = *reinterpret_cast<const f4a*>(rp + i0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (x0 + j >= W) p[j] = 0.0f;
+        const float pr = win[1][j + 1] * rv[j];
+        accr = accr + pr;
+      }
+      const f4a out = {p[0], p[1], p[2], p[3]};
+      *reinterpret_cast<f4a*>(pred + (y + 1) * ps + 4 + x0) = out;
+    }
+    accr = wave_sum(accr);
+    if (lane == 0) red[wave * kQ + u] = accr;  // read behind the first block's barrier
+
+    float vb = 0.0f;
+    int ib = 0;
+    for (int kb = 0; kb < K; kb += kLaK, buf ^= 1) {
+      float* sb = sums + buf * kLaSums;
+      const int nk = K - kb < kLaK ? K - kb : kLaK;
+      float v[64];
+      switch (nk) {
+        case 1: lookahead_block<1>(a, pred, sCode, sLX, ltt, kb, tid, ps, wp, NP, qy0, qx0, qdy, qdx, v); break;
+        case 2: lookahead_block<2>(a, pred, sCode, sLX, ltt, kb, tid, ps, wp, NP, qy0, qx0, qdy, qdx, v); break;
+        case 3: lookahead_block<3>(a, pred, sCode, sLX, ltt, kb, tid, ps, wp, NP, qy0, qx0, qdy, qdx, v); break;
+        default: lookahead_block<4>(a, pred, sCode, sLX, ltt, kb, tid, ps, wp, NP, qy0, qx0, qdy, qdx, v);
+      }
+      sb[lane * 4 + wave] = wave_sum_scatter64(v);
+      __syncthreads();
+      const float* sz = sb + (lane & (kLaZ - 1)) * (kLaK * 4);
+#pragma unroll
+      for (int q = 0; q < kLaK; ++q) {
+        if (q < nk) {
+          const f4a w = *reinterpret_cast<const f4a*>(sz + 4 * q);
+          const float s = ((w[0] + w[1]) + w[2]) + w[3];
+          if (kb + q == 0) vb = s;
+          else if (vb < s) { vb = s; ib = kb + q; }
+        }
+      }
+    }
+    float S = 0.0f;
+#pragma unroll
+    for (int z = 0; z < kLaZ; ++z)
+      S = S + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vb), z));
+    const float rew = ((red[u] + red[kQ + u]) + red[2 * kQ + u]) + red[3 * kQ + u];
+    const float gs = a.gamma * S;
+    const float q = rew + gs;
+    if (u == 0) qbest = q;
+    else if (qbest < q) { qbest = q; best = u; }
+    if (a.tr_q && tid == 0) a.tr_q[at * kQ + u] = q;
+    if (a.tr_rew && tid == 0) a.tr_rew[at * kQ + u] = rew;
+    if (a.tr_lmax && tid < kLaZ) {
+      a.tr_lmax[(at * kQ + u) * kLaZ + tid] = vb;
+      a.tr_lidx[(at * kQ + u) * kLaZ + tid] = ib;
+    }
+  }
+  return best;
+}
+
+// POLICY: 0 mode, 1 QMDP, 2 the alpha-vector policy (alpha_control), 3 the
+// one-step lookahead over the alpha vectors (lookahead_control).
 template <int POLICY>
 __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -343,6 +564,12 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
     if (r < L.prows && y >= 0 && y < H && x >= 0 && x < W) v = a.code[(long long)y * wp + x];
     sCode[i] = v;
   }
+  if constexpr (POLICY == 3) {
+    // the L columns transposed, [class][16 z]: a cell's sixteen L_z in one row
+    float* ltt = lds + L.total + 2 * kLaSums;
+    for (int i = tid; i < kLaZ * kResLK; i += kEpThreads)
+      ltt[i] = a.rfact[kResLT + (i & (kLaZ - 1)) * kResLK + (i >> 4)];
+  }
 
   for (int e = blockIdx.x; e < a.episodes; e += gridDim.x) {
     __syncthreads();  // the previous episode's planes are no longer read
@@ -373,7 +600,9 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
     for (int k = 0; k < a.horizon && status == 0; ++k) {
       // 1. control: the lane's partials
       int u = 0, mcell = 0;
-      if constexpr (POLICY == 2) {
+      if constexpr (POLICY == 3) {
+        u = lookahead_control(a, L, lds, cur, nxt, sc, k, e, qy0, qx0, qdy, qdx);
+      } else if constexpr (POLICY == 2) {
         u = alpha_control(a, L, lds, cur, sc, k, e, qy0, qx0, qdy, qdx);
       } else {
       if constexpr (POLICY == 1) {
@@ -594,10 +823,16 @@ hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const Plan
 }
 
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups) {
-  const long long bytes =
-      policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K) : episode_lds_bytes(a.g, a.E);
+  const long long bytes = policy == 3   ? episode_lookahead_lds_bytes(a.g, a.E)
+                          : policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K)
+                                        : episode_lds_bytes(a.g, a.E);
   if (bytes > (long long)kDictLdsMaxBytes || workgroups < 1) return hipErrorInvalidValue;
-  if (policy == 2) {
+  if (policy == 3) {
+    if (!a.alpha || !a.rplanes || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<3>), attr);
+    hipLaunchKernelGGL(k_episodes<3>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
+  } else if (policy == 2) {
     if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
     static unsigned long long attr = 0;
     allow_lds(reinterpret_cast<const void*>(&k_episodes<2>), attr);

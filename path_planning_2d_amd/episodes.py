@@ -1,10 +1,11 @@
 """Batched closed-loop policy episodes (include/pp2.h "episodes").
 
 ``EpisodeBatch`` runs E simulated robots under a control policy -- the
-belief-mode policy of the reference MDP node, the QMDP policy, or the greedy
-policy of the FIB alphas or of the PBVI alpha vectors -- each with its own
-belief, for up to ``horizon`` steps in one kernel launch, and returns
-how the policy did: steps to the goal, status and discounted cost per episode.
+belief-mode policy of the reference MDP node, the QMDP policy, the greedy
+policy of the FIB alphas or of the PBVI alpha vectors, or the one-step
+lookahead over either set -- each with its own belief, for up to ``horizon``
+steps in one kernel launch, and returns how the policy did: steps to the goal,
+status and discounted cost per episode.
 Everything runs in libpp2_hip.so; there is no CPU path.
 """
 from __future__ import annotations
@@ -26,6 +27,8 @@ STATUS_LOST = 2      # the belief update left no finite positive value
 ALPHA_FIB = 0        # the context's current FIB alphas (K = 9, action of vector k = k)
 ALPHA_PBVI = 1       # the context's PBVI alpha vectors and their actions (K = S)
 _ALPHA_SETS = {"fib": ALPHA_FIB, "pbvi": ALPHA_PBVI}
+# ``run``'s names of the one-step lookahead over a set
+_LOOKAHEAD = {"fib-lookahead": "fib", "pbvi-lookahead": "pbvi"}
 
 
 def _i32(a):
@@ -50,7 +53,8 @@ class EpisodeBatch:
         self.record_trace = bool(record_trace)
         self.cells = ctx.cells
         self.policy = None
-        self.alpha_set = None    # of the last run, if that was an alpha run
+        self.alpha_set = None    # of the last run, if that was an alpha or a lookahead run
+        self.lookahead = False   # the last run was a lookahead run
         h = C.c_void_p()
         call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
              int(self.record_trace))
@@ -105,22 +109,22 @@ class EpisodeBatch:
     def run(self, policy, b0, start_cells, seed: int = 0):
         """Enqueue one batch: every episode starts from belief ``b0`` with its
         true robot at ``start_cells[e]`` (``y * W + x``).  ``policy``: "mode",
-        "qmdp" (or CONTROL_MODE / CONTROL_QMDP), or "fib" / "pbvi", which are
-        ``run_alpha``.  Asynchronous."""
+        "qmdp" (or CONTROL_MODE / CONTROL_QMDP), "fib" / "pbvi", which are
+        ``run_alpha``, or "fib-lookahead" / "pbvi-lookahead", which are
+        ``run_lookahead``.  Asynchronous."""
         if isinstance(policy, str) and policy in _ALPHA_SETS:
             return self.run_alpha(policy, b0, start_cells, seed)
+        if isinstance(policy, str) and policy in _LOOKAHEAD:
+            return self.run_lookahead(_LOOKAHEAD[policy], b0, start_cells, seed)
         policy, b0, start, seed = self.check_run_args(self.cells, self.episodes, policy, b0,
                                                       start_cells, seed)
         call("pp2_episodes_run", self._h, policy, C.c_uint64(seed), _f32(b0), _i32(start))
         self.policy = policy
         self.alpha_set = None
+        self.lookahead = False
         return self
 
-    def run_alpha(self, alpha_set, b0, start_cells, seed: int = 0):
-        """``run`` under the greedy policy of an alpha-vector set: "fib" (or
-        ALPHA_FIB), the context's current FIB alphas, or "pbvi" (ALPHA_PBVI),
-        its PBVI alpha vectors.  The cost stays the MDP cost, so all four
-        policies are compared on one scale.  Asynchronous."""
+    def _check_alpha_args(self, alpha_set, b0, start_cells, seed):
         if isinstance(alpha_set, str):
             if alpha_set not in _ALPHA_SETS:
                 raise ValueError(f"unknown alpha set {alpha_set!r}")
@@ -132,10 +136,33 @@ class EpisodeBatch:
         # argument only has to be a valid one)
         _, b0, start, seed = self.check_run_args(self.cells, self.episodes,
                                                  GridContext.CONTROL_QMDP, b0, start_cells, seed)
-        call("pp2_episodes_run_alpha", self._h, int(alpha_set), C.c_uint64(seed), _f32(b0),
+        return int(alpha_set), b0, start, seed
+
+    def run_alpha(self, alpha_set, b0, start_cells, seed: int = 0):
+        """``run`` under the greedy policy of an alpha-vector set: "fib" (or
+        ALPHA_FIB), the context's current FIB alphas, or "pbvi" (ALPHA_PBVI),
+        its PBVI alpha vectors.  The cost stays the MDP cost, so all
+        policies are compared on one scale.  Asynchronous."""
+        alpha_set, b0, start, seed = self._check_alpha_args(alpha_set, b0, start_cells, seed)
+        call("pp2_episodes_run_alpha", self._h, alpha_set, C.c_uint64(seed), _f32(b0),
              _i32(start))
         self.policy = None
-        self.alpha_set = int(alpha_set)
+        self.alpha_set = alpha_set
+        self.lookahead = False
+        return self
+
+    def run_lookahead(self, alpha_set, b0, start_cells, seed: int = 0):
+        """``run`` under the one-step lookahead policy over an alpha-vector set
+        ("fib" / "pbvi", as ``run_alpha``): the action with the largest
+        Q(b, u) = <b, R_u> + gamma * sum_z max_k <L_z . T_u^T b, alpha_k>, the
+        reference POMDP node's tree at depth 1 with exact observation
+        weights.  Asynchronous."""
+        alpha_set, b0, start, seed = self._check_alpha_args(alpha_set, b0, start_cells, seed)
+        call("pp2_episodes_run_lookahead", self._h, alpha_set, C.c_uint64(seed), _f32(b0),
+             _i32(start))
+        self.policy = None
+        self.alpha_set = alpha_set
+        self.lookahead = True
         return self
 
     def results(self) -> dict:
@@ -150,7 +177,8 @@ class EpisodeBatch:
 
     def trace(self) -> dict:
         """The last run's per-step record, [horizon, E] arrays (qsums
-        [horizon, E, 9]: QMDP's S_u or a FIB run's V_k, else 0; mode_cells only
+        [horizon, E, 9]: QMDP's S_u, a FIB run's V_k or a lookahead run's Q_u,
+        else 0; mode_cells only
         for mode runs).  Steps not taken hold 255, 255, -1, 0, -1."""
         sh = (self.horizon, self.episodes)
         a = np.empty(sh, np.uint8)
@@ -170,8 +198,22 @@ class EpisodeBatch:
         call("pp2_episodes_trace_alpha", self._h, _i32(best), _f32(vsum))
         return {"best_index": best, "best_sum": vsum}
 
+    def trace_lookahead(self) -> dict:
+        """The last lookahead run's record: ``q`` and ``rewards`` [horizon, E,
+        9] (Q_u, <b, R_u>), ``leaf_max`` and ``leaf_index`` [horizon, E, 9, 16]
+        (per (u, z) the largest <raw_uz, alpha_k> and its k).  Steps not taken
+        hold 0, 0, 0, -1."""
+        sh = (self.horizon, self.episodes)
+        q = np.empty(sh + (9,), np.float32)
+        rew = np.empty(sh + (9,), np.float32)
+        lmax = np.empty(sh + (9, 16), np.float32)
+        lidx = np.empty(sh + (9, 16), np.int32)
+        call("pp2_episodes_trace_lookahead", self._h, _f32(q), _f32(rew), _f32(lmax), _i32(lidx))
+        return {"q": q, "rewards": rew, "leaf_max": lmax, "leaf_index": lidx}
+
     def alphas(self):
-        """(alphas[K, hw], actions[K]): the alpha set the last alpha run read."""
+        """(alphas[K, hw], actions[K]): the alpha set the last alpha or
+        lookahead run read."""
         k = C.c_int(0)
         call("pp2_episodes_get_alpha", self._h, C.byref(k), None, None)
         al = np.empty((k.value, self.cells), np.float32)
