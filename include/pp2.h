@@ -515,7 +515,26 @@ int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
  * one workgroup per episode, the belief in LDS.  Needs an unsharded context
  * with a model, current J and A, and an active dictionary-coded model with
  * factored rows (pp2_model_dict_info), whose belief fits the LDS of one
- * workgroup (100x40 and 97x131 do, 256x256 does not: PP2_EINVAL).
+ * workgroup (100x40 and 97x131 do, 256x256 does not: PP2_EINVAL) -- unless
+ * the batch was created with another placement of the belief:
+ *
+ * Placement (pp2_episodes_create_placed).  An episode's two belief planes live
+ * in the LDS of its workgroup (PP2_EPISODES_LDS, pp2_episodes_create's) or in
+ * device memory (PP2_EPISODES_GLOBAL), which admits any grid the context
+ * supports; PP2_EPISODES_AUTO decides per launch: LDS if that launch's LDS
+ * layout fits (an alpha run's is larger than a MODE / QMDP run's), else device
+ * memory.  The placement changes no result: every step below, every rounding,
+ * the pinned Q-dot order, the random numbers, statuses and traces are the
+ * same bits from either.  The device-memory planes are one scratch per batch,
+ * allocated (and zeroed, once) at the first launch that needs it, never at
+ * create -- PP2_ENOMEM if that fails, the batch stays usable -- and freed by
+ * pp2_episodes_destroy: per workgroup two fp32 planes [H + 2][stride + 4] + 4
+ * (zero halo rows and x pads, rounded up to 256 bytes), then one padded image
+ * of b0 and one padded uint16 code plane, both rebuilt by every such run and
+ * shared by all workgroups.  Workgroups of such a launch = min(episodes,
+ * CUs x 4, what 1 GiB of scratch holds), at least 1.  MODE, QMDP and alpha
+ * runs (FIB, and PBVI with any K <= 4096) take either placement; the
+ * lookahead runs from LDS only.
  *
  * Episode e: true cell s = start_cells[e] (y*W + x), stored belief b = b0,
  * cost G = +0, discount d = 1.  If s is the goal: steps 0, status 1, belief
@@ -610,6 +629,19 @@ typedef struct pp2_episodes pp2_episodes;
 int pp2_episodes_create(pp2_episodes** out, pp2_ctx* ctx, int episodes, int horizon,
                         int record_trace);
 int pp2_episodes_destroy(pp2_episodes* ep);
+#define PP2_EPISODES_LDS    0  /* pp2_episodes_create's behaviour: planes in LDS, PP2_EINVAL if they do not fit */
+#define PP2_EPISODES_GLOBAL 1  /* planes in device memory, any grid the context supports */
+#define PP2_EPISODES_AUTO   2  /* per launch: LDS if that launch's LDS layout fits, else device memory */
+/* pp2_episodes_create with a placement of the belief planes ("Placement"
+ * above); pp2_episodes_create is placement PP2_EPISODES_LDS.  Every check of
+ * pp2_episodes_create holds, except that PP2_EPISODES_GLOBAL and
+ * PP2_EPISODES_AUTO do not refuse a grid for its LDS size.  PP2_EINVAL: an
+ * unknown placement. */
+int pp2_episodes_create_placed(pp2_episodes** out, pp2_ctx* ctx, int episodes, int horizon,
+                               int record_trace, int placement);
+/* requested placement, placement of the last launch (-1 before any run),
+ * bytes of device scratch held for the global planes (0 until first needed); any may be NULL */
+int pp2_episodes_placement(pp2_episodes* ep, int* requested, int* last, long long* scratch_bytes);
 /* b0: hw floats, every entry finite and >= +0; start_cells: [episodes] in
  * [0, hw) (else PP2_EINVAL).  Settles pending work of the context first and
  * re-checks its model, then reads the current J and A.  Asynchronous. */
@@ -633,7 +665,9 @@ int pp2_episodes_get_belief(pp2_episodes* ep, int episode, float* belief);
 int pp2_episodes_get_q(pp2_episodes* ep, float* Q);
 /* LDS bytes per workgroup, workgroups and threads per workgroup of the last
  * launch (before any run: of a MODE / QMDP launch; an alpha launch adds its
- * scratch for K != 9, a lookahead launch its own) */
+ * scratch for K != 9, a lookahead launch its own; a device-memory launch
+ * keeps only the tables and reduction scratch in LDS and reports that, and
+ * its own workgroups) */
 int pp2_episodes_info(pp2_episodes* ep, int* lds_bytes, int* workgroups, int* threads);
 #define PP2_ALPHA_FIB  0   /* the context's current FIB alphas: K = 9, action of vector k = k */
 #define PP2_ALPHA_PBVI 1   /* the context's PBVI alpha vectors and their actions: K = S */
@@ -657,7 +691,9 @@ int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t*
 /* pp2_episodes_run with the one-step lookahead policy over an alpha set
  * ("Lookahead runs" above): arguments, checks, statuses and asynchrony are
  * those of pp2_episodes_run_alpha; PP2_EINVAL before any launch also when the
- * workgroup's LDS with the lookahead scratch does not fit.  Afterwards
+ * workgroup's LDS with the lookahead scratch does not fit -- also on a
+ * PP2_EPISODES_AUTO batch -- and on every PP2_EPISODES_GLOBAL batch: the
+ * lookahead runs from LDS planes only.  Afterwards
  * pp2_episodes_trace returns actions, observations and cells as usual, qsums =
  * the nine Q_u and mode_cells = -1; pp2_episodes_get_alpha answers with the
  * set read; pp2_episodes_trace_alpha and pp2_episodes_get_q return PP2_ESTATE;

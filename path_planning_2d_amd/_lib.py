@@ -113,6 +113,9 @@ SIGNATURES = {
     "pp2_rollout_get_belief": [_vp, C.c_int, _f32p],
     "pp2_episodes_create": [C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int],
     "pp2_episodes_destroy": [_vp],
+    "pp2_episodes_create_placed": [C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, C.c_int],
+    "pp2_episodes_placement": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                               C.POINTER(C.c_longlong)],
     "pp2_episodes_run": [_vp, C.c_int, C.c_uint64, _f32p, C.POINTER(C.c_int32)],
     "pp2_episodes_results": [_vp, C.POINTER(C.c_int32), _u8p, _f32p, C.POINTER(C.c_int32)],
     "pp2_episodes_trace": [_vp, _u8p, _u8p, C.POINTER(C.c_int32), _f32p, C.POINTER(C.c_int32)],

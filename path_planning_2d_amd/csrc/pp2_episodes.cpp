@@ -4,6 +4,10 @@
 // PBVI alpha vectors instead, a lookahead run those and the reward planes --
 // and one launch of the persistent episode kernel
 // on the context's stream; results, traces and beliefs are copied back on demand.
+// A batch created with pp2_episodes_create_placed may keep the belief planes in
+// device memory instead of LDS (pp2_episodes.h "Placement"): such a launch is
+// preceded by the kernel that pads the code plane and b0, and works in a
+// scratch allocated at the first such launch.
 #include <cstring>
 #include <vector>
 
@@ -20,7 +24,14 @@ struct pp2_episodes {
   int policy = -1;             // of the last run (-1: none yet; 2: an alpha run; 3: a lookahead run)
   int alpha_set = -1;          // of the last run, if that was an alpha or a lookahead run
   int lds_bytes = 0, workgroups = 0;  // of the last launch (before any: MODE / QMDP's)
-  int base_workgroups = 0;     // of a MODE / QMDP launch
+  int base_workgroups = 0;     // of a MODE / QMDP launch from LDS
+  int placement = PP2_EPISODES_LDS;  // as requested at create
+  int last_placement = -1;     // of the last launch (-1: none yet)
+  // the global placement's scratch, from the first global launch on:
+  // [scratch_wgs][2] planes of ep_plane_stride floats | padded b0 | padded code
+  char* d_scratch = nullptr;
+  long long scratch_bytes = 0;
+  int scratch_wgs = 0;
   float* d_alpha = nullptr;    // [alpha_cap][H][wp], from the first alpha run on
   uint8_t* d_alpha_act = nullptr;  // [alpha_cap]
   int alpha_cap = 0, alpha_k = 0;  // vectors allocated, vectors of the last alpha run
@@ -52,7 +63,9 @@ namespace {
 
 // What a batch needs of its context, at create and again at every run (the
 // model may have been replaced in between).
-int check_episode_ctx(pp2_ctx* c, const pp2_episodes* ep, long long* lds_bytes) {
+// must_fit: the LDS placement, whose MODE / QMDP layout has to fit.
+int check_episode_ctx(pp2_ctx* c, const pp2_episodes* ep, long long* lds_bytes,
+                      bool must_fit = true) {
   CHECK(check_model(c));
   if (c->nranks > 1 || c->group || c->g.rows != c->g.grows || c->g.halo != 1)
     return set_err(PP2_ESTATE, "episodes run on an unsharded context");
@@ -63,7 +76,7 @@ int check_episode_ctx(pp2_ctx* c, const pp2_episodes* ep, long long* lds_bytes) 
   if (ep && (ep->H != c->g.rows || ep->W != c->g.width || ep->wp != c->g.wp))
     return set_err(PP2_ESTATE, "the context's geometry changed since pp2_episodes_create");
   const long long bytes = pp2::episode_lds_bytes(c->g, c->dict_n);
-  if (bytes > (long long)pp2::kDictLdsMaxBytes)
+  if (must_fit && bytes > (long long)pp2::kDictLdsMaxBytes)
     return set_err(PP2_EINVAL,
                    "a %d x %d belief needs %lld bytes of LDS per episode (at most %zu fit)",
                    c->g.width, c->g.rows, bytes, pp2::kDictLdsMaxBytes);
@@ -123,6 +136,28 @@ int episode_workgroups(const pp2_ctx* c, int episodes, long long lds,
   return (int)(episodes < cap ? episodes : cap);
 }
 
+// The global placement's scratch: bytes of the two planes of a workgroup, of
+// the images every workgroup shares, and the workgroups of a launch =
+// min(episodes, CUs x kEpGlobalPerCu, what kEpScratchCapBytes holds), at least 1.
+struct ScratchPlan {
+  long long stride, per_wg, shared, bytes;
+  int workgroups;
+};
+ScratchPlan scratch_plan(const pp2_ctx* c, int episodes) {
+  ScratchPlan p;
+  p.stride = pp2::ep_plane_stride(c->g);
+  p.per_wg = 2 * p.stride * (long long)sizeof(float);
+  p.shared = p.stride * (long long)sizeof(float) +
+             pp2::ep_code_elems(c->g) * (long long)sizeof(uint16_t);
+  long long w = (long long)(c->ncus > 0 ? c->ncus : 256) * pp2::kEpGlobalPerCu;
+  const long long fit = (pp2::kEpScratchCapBytes - p.shared) / p.per_wg;
+  w = w < episodes ? w : episodes;
+  w = w < fit ? w : fit;
+  p.workgroups = (int)(w < 1 ? 1 : w);
+  p.bytes = p.workgroups * p.per_wg + p.shared;
+  return p;
+}
+
 // One run.  policy: PP2_CONTROL_MODE / PP2_CONTROL_QMDP, or kPolicyAlpha /
 // kPolicyLookahead with alpha_set PP2_ALPHA_FIB / PP2_ALPHA_PBVI (all checked
 // by the callers).
@@ -133,7 +168,7 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   const bool alpha = policy == kPolicyAlpha || look;  // reads an alpha set
   // settles pending resident launches first: J and A below are the current ones
   long long lds = 0;
-  CHECK(check_episode_ctx(c, ep, &lds));
+  CHECK(check_episode_ctx(c, ep, &lds, ep->placement == PP2_EPISODES_LDS));
   const int H = ep->H, W = ep->W, wp = ep->wp, E = ep->episodes;
   const size_t hw = (size_t)H * W;
   // the alpha set: the context's current one
@@ -152,11 +187,33 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     }
     lds = look ? pp2::episode_lookahead_lds_bytes(c->g, c->dict_n)
                : pp2::episode_alpha_lds_bytes(c->g, c->dict_n, K);
+  }
+  // where this launch's planes live: AUTO takes LDS if this launch's layout fits
+  const bool fits = lds <= (long long)pp2::kDictLdsMaxBytes;
+  const bool global = ep->placement == PP2_EPISODES_GLOBAL ||
+                      (ep->placement == PP2_EPISODES_AUTO && !fits);
+  if (look && ep->placement == PP2_EPISODES_GLOBAL)
+    return set_err(PP2_EINVAL,
+                   "the lookahead runs from LDS planes only: the batch was created with "
+                   "PP2_EPISODES_GLOBAL");
+  if (look && global)
+    return set_err(PP2_EINVAL,
+                   "the lookahead runs from LDS planes only, and a %d x %d belief with the "
+                   "lookahead scratch needs %lld bytes of LDS per episode (at most %zu fit)",
+                   W, H, lds, pp2::kDictLdsMaxBytes);
+  if (!global && !fits)  // (the LDS placement's alpha and lookahead layouts)
+    return set_err(PP2_EINVAL,
+                   "a %d x %d belief with the %s scratch needs %lld bytes of LDS per "
+                   "episode (at most %zu fit)",
+                   W, H, look ? "lookahead" : "alpha", lds, pp2::kDictLdsMaxBytes);
+  ScratchPlan plan{};
+  if (global) {
+    lds = pp2::episode_global_lds_bytes(c->dict_n,
+                                        policy == kPolicyAlpha ? pp2::ep_alpha_floats(K) : 0);
     if (lds > (long long)pp2::kDictLdsMaxBytes)
-      return set_err(PP2_EINVAL,
-                     "a %d x %d belief with the %s scratch needs %lld bytes of LDS per "
-                     "episode (at most %zu fit)",
-                     W, H, look ? "lookahead" : "alpha", lds, pp2::kDictLdsMaxBytes);
+      return set_err(PP2_EINVAL, "the tables of %d dictionary entries need %lld bytes of LDS",
+                     c->dict_n, lds);
+    plan = scratch_plan(c, ep->episodes);
   }
   for (size_t i = 0; i < hw; ++i) {
     uint32_t bits;
@@ -171,6 +228,20 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   // the staging vectors may still feed the previous run's copies
   HIPCHK(hipStreamSynchronize(c->stream));
   const size_t np = (size_t)H * wp, HE = (size_t)ep->horizon * E;
+  if (global && !ep->d_scratch) {
+    // the first global launch: planes zeroed once (halo rows and x pads stay
+    // zero, the steps store interior quads only).  A failure leaves the batch
+    // as it was.
+    CHECK(dev_alloc(&ep->d_scratch, (size_t)plan.bytes, "episode planes"));
+    if (hipMemsetAsync(ep->d_scratch, 0, (size_t)plan.bytes, c->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(ep->d_scratch);
+      ep->d_scratch = nullptr;
+      return set_err(PP2_EHIP, "hipMemsetAsync episode planes");
+    }
+    ep->scratch_bytes = plan.bytes;
+    ep->scratch_wgs = plan.workgroups;
+  }
   if (alpha) {
     // a PBVI action the tables have no row for: before any launch.  Checked
     // once per version of the set (a copy to the host and a synchronise), not
@@ -205,7 +276,8 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     }
   }
   ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
-  ep->workgroups = look    ? episode_workgroups(c, E, lds, kLookaheadPerCu)
+  ep->workgroups = global  ? ep->scratch_wgs
+                   : look  ? episode_workgroups(c, E, lds, kLookaheadPerCu)
                    : alpha ? episode_workgroups(c, E, lds)
                            : ep->base_workgroups;
   for (int y = 0; y < H; ++y)
@@ -288,7 +360,20 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
       a.tr_bsum = ep->d_trbsum;
     }
   }
-  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups));
+  if (global) {
+    // the padded code plane and b0 image of this run (the model may have been
+    // replaced since the last one), then the global instance
+    const long long stride = pp2::ep_plane_stride(c->g);
+    a.gplanes = reinterpret_cast<float*>(ep->d_scratch);
+    a.gstride = stride;
+    float* gb0 = a.gplanes + (long long)ep->scratch_wgs * 2 * stride;
+    uint16_t* gcode = reinterpret_cast<uint16_t*>(gb0 + stride);
+    a.gb0 = gb0;
+    a.gcode = gcode;
+    HIPCHK(pp2::launch_episode_pad(c->stream, c->g, c->d_code, ep->d_b0, gcode, gb0));
+  }
+  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups, global));
+  ep->last_placement = global ? PP2_EPISODES_GLOBAL : PP2_EPISODES_LDS;
   ep->policy = policy;
   ep->alpha_set = alpha ? alpha_set : -1;
   if (alpha) ep->alpha_k = K;
@@ -309,7 +394,7 @@ int pp2_episodes_destroy(pp2_episodes* ep) {
                   (void*)ep->d_trmode, (void*)ep->d_trq, (void*)ep->d_alpha,
                   (void*)ep->d_alpha_act, (void*)ep->d_trbest, (void*)ep->d_trbsum,
                   (void*)ep->d_rplanes, (void*)ep->d_larew, (void*)ep->d_lamax,
-                  (void*)ep->d_laidx})
+                  (void*)ep->d_laidx, (void*)ep->d_scratch})
     if (p) (void)hipFree(p);
   delete ep;
   return PP2_OK;
@@ -317,6 +402,11 @@ int pp2_episodes_destroy(pp2_episodes* ep) {
 
 int pp2_episodes_create(pp2_episodes** out, pp2_ctx* c, int episodes, int horizon,
                         int record_trace) {
+  return pp2_episodes_create_placed(out, c, episodes, horizon, record_trace, PP2_EPISODES_LDS);
+}
+
+int pp2_episodes_create_placed(pp2_episodes** out, pp2_ctx* c, int episodes, int horizon,
+                               int record_trace, int placement) {
   if (!out) return set_err(PP2_EINVAL, "out is null");
   *out = nullptr;
   if (!c) return set_err(PP2_EINVAL, "null context");
@@ -324,19 +414,31 @@ int pp2_episodes_create(pp2_episodes** out, pp2_ctx* c, int episodes, int horizo
     return set_err(PP2_EINVAL, "episodes %d outside 1..131072", episodes);
   if (horizon < 1 || horizon > 4096)
     return set_err(PP2_EINVAL, "horizon %d outside 1..4096", horizon);
+  if (placement != PP2_EPISODES_LDS && placement != PP2_EPISODES_GLOBAL &&
+      placement != PP2_EPISODES_AUTO)
+    return set_err(PP2_EINVAL, "unknown placement %d", placement);
   long long lds = 0;
-  CHECK(check_episode_ctx(c, nullptr, &lds));
+  CHECK(check_episode_ctx(c, nullptr, &lds, placement == PP2_EPISODES_LDS));
   DeviceGuard dg(c->device);
   pp2_episodes* ep = new pp2_episodes();
   ep->ctx = c;
+  ep->placement = placement;
   ep->episodes = episodes;
   ep->horizon = horizon;
   ep->trace = record_trace != 0;
   ep->H = c->g.rows;
   ep->W = c->g.width;
   ep->wp = c->g.wp;
-  ep->lds_bytes = (int)lds;
-  ep->workgroups = ep->base_workgroups = episode_workgroups(c, episodes, lds);
+  ep->base_workgroups = episode_workgroups(c, episodes, lds);
+  if (placement == PP2_EPISODES_GLOBAL ||
+      (placement == PP2_EPISODES_AUTO && lds > (long long)pp2::kDictLdsMaxBytes)) {
+    // what a MODE / QMDP launch of this batch will take
+    ep->lds_bytes = (int)pp2::episode_global_lds_bytes(c->dict_n, 0);
+    ep->workgroups = scratch_plan(c, episodes).workgroups;
+  } else {
+    ep->lds_bytes = (int)lds;
+    ep->workgroups = ep->base_workgroups;
+  }
   const size_t np = (size_t)ep->H * ep->wp, E = (size_t)episodes, HE = (size_t)horizon * E;
   auto fail = [&](int s) {
     pp2_episodes_destroy(ep);
@@ -500,6 +602,14 @@ int pp2_episodes_get_q(pp2_episodes* ep, float* Q) {
     for (int x = 0; x < ep->W; ++x)
       for (int u = 0; u < 9; ++u)
         Q[((size_t)y * ep->W + x) * 9 + u] = planes[u * np + (size_t)y * ep->wp + x];
+  return PP2_OK;
+}
+
+int pp2_episodes_placement(pp2_episodes* ep, int* requested, int* last, long long* scratch_bytes) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (requested) *requested = ep->placement;
+  if (last) *last = ep->last_placement;
+  if (scratch_bytes) *scratch_bytes = ep->scratch_bytes;
   return PP2_OK;
 }
 

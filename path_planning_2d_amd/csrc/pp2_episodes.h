@@ -24,6 +24,26 @@
 //   ltt    ... then the L columns transposed, [kResLK classes][16 z]
 // with ps = wp + 4: cell (y, x) of a plane sits at (y + 1) * ps + 4 + x, so
 // x = -1 is the row's last left pad and x = wp the next row's first.
+//
+// Placement.  The above is the LDS placement (PP2_EPISODES_LDS), which admits
+// the grids whose planes fit kDictLdsMaxBytes.  The global placement
+// (PP2_EPISODES_GLOBAL; k_episodes<POLICY, true>, policies 0..2) keeps the
+// tables, red and asum in LDS -- ct | rf | cls | red | asum, episode_lds_global
+// -- and the planes in one device allocation of the batch (the scratch):
+//   planes  [workgroups][2] belief planes of ep_plane_stride floats, the LDS
+//           planes' own indexing; zeroed once when allocated: a step writes the
+//           interior quads only, so halo rows and x pads stay zero
+//   b0img   the padded image of b0, same indexing, built per run
+//           (k_episode_pad): step 0 of every episode reads it in place of a
+//           per-episode copy, and an episode without a step stores it
+//   code    the padded uint16 code plane, built per run, read by all
+// Workgroups of a global launch = min(episodes, CUs x per-CU count,
+// kEpScratchCapBytes / bytes of a workgroup's two planes), at least 1; the
+// per-CU count is what the instance's registers admit, at most kEpMaxPerCu.  A
+// workgroup is one wave per SIMD, and the three global instances take 121
+// (MODE), 127 (QMDP) and 118 (alpha) VGPRs, which is 4 waves per SIMD
+// (512 / 128): kEpGlobalPerCu = 4.  More workgroups than that would only queue
+// behind the resident ones and widen the scratch.
 #pragma once
 #include "pp2_internal.h"
 
@@ -32,6 +52,10 @@ namespace pp2 {
 constexpr int kEpThreads = 256;
 constexpr int kEpRedFloats = 48;
 constexpr int kEpMaxPerCu = 8;  // workgroups per CU the grid is sized for
+// global placement: workgroups per CU by the instances' VGPRs (see above), and
+// the cap on the scratch that holds every workgroup's two planes
+constexpr int kEpGlobalPerCu = 4;
+constexpr long long kEpScratchCapBytes = 1LL << 30;
 // The alpha-vector policy (k_episodes<2>): K vectors in blocks of
 // kEpAlphaBlock accumulators, their per-wave sums staged per chunk of
 // kEpAlphaChunk vectors (one barrier per chunk, two buffers).  K = 9 (FIB)
@@ -77,6 +101,33 @@ __host__ __device__ inline EpisodeLds episode_lds(const Geom& g, int E) {
   l.b1 = l.b0 + plane;
   l.total = l.b1 + plane;
   return l;
+}
+// The global placement's LDS: the tables and red (code, b0, b1 unused).
+__host__ __device__ inline EpisodeLds episode_lds_global(const Geom& g, int E) {
+  EpisodeLds l;
+  l.ps = g.wp + 4;
+  l.prows = g.rows + 2;
+  l.epad = ep_pad4(E);
+  l.ct = 0;
+  l.rf = l.ct + kEpCtFloats;
+  l.cls = l.rf + ep_pad4(kResTab + ((E + 3) >> 2));
+  l.code = l.b0 = l.b1 = 0;
+  l.red = ep_table_floats(E);
+  l.total = l.red + kEpRedFloats;
+  return l;
+}
+// ... its bytes (alpha_floats: ep_alpha_floats(K) of an alpha run, else 0)
+inline long long episode_global_lds_bytes(int E, int alpha_floats) {
+  return 4LL * (ep_table_floats(E) + kEpRedFloats + alpha_floats);
+}
+// floats from one global plane to the next (a multiple of 64: 256-byte
+// aligned planes), and uint16 of the padded code plane
+inline long long ep_plane_stride(const Geom& g) {
+  const long long plane = ((long long)g.rows + 2) * (g.wp + 4) + 4;
+  return (plane + 63) & ~63LL;
+}
+inline long long ep_code_elems(const Geom& g) {
+  return (((long long)g.rows + 2) * (g.wp + 4) + 8 + 7) & ~7LL;
 }
 // LDS bytes of one workgroup; a batch is admitted only if this is at most
 // kDictLdsMaxBytes (64-bit: the planes of a large grid overflow int floats).
@@ -132,6 +183,12 @@ struct EpisodeRun {
   float* tr_rew;             // [horizon][episodes][9]
   float* tr_lmax;            // [horizon][episodes][9][16]
   int32_t* tr_lidx;
+  // global placement: workgroup w's planes at gplanes + w * 2 * gstride, the
+  // padded b0 image and the padded code plane (null in an LDS launch)
+  float* gplanes;
+  long long gstride;         // floats of a plane (ep_plane_stride)
+  const float* gb0;
+  const uint16_t* gcode;
 };
 
 // Q[u][y][x] = k_mdp_sweep's cost of action u from J (sparse coded model).
@@ -147,6 +204,13 @@ hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const Plan
 // policy: PP2_CONTROL_MODE (0), PP2_CONTROL_QMDP (1), 2, the alpha-vector
 // policy over a.alpha, or 3, the one-step lookahead over a.alpha and
 // a.rplanes.  hipErrorInvalidValue when the workgroup's LDS does not fit.
-hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups);
+// global: the global-placement instance (policies 0..2; a.gplanes, a.gb0 and
+// a.gcode set, built by launch_episode_pad on the same stream).
+hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
+                           bool global = false);
+// The padded images of a global launch: gcode[(y + 1) * ps + 4 + x] = code of
+// cell (y, x), gb0 likewise from b0 [H][wp]; everything off the grid 0.
+hipError_t launch_episode_pad(hipStream_t st, const Geom& g, const uint16_t* code,
+                              const float* b0, uint16_t* gcode, float* gb0);
 
 }  // namespace pp2

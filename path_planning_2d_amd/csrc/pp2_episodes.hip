@@ -5,6 +5,9 @@
 // move the true robot, sample the observation, update the belief -- each
 // wholly inside one workgroup whose LDS holds the episode's belief
 // (pp2_episodes.h has the LDS layout, include/pp2.h "episodes" the semantics).
+// The global placement's instances (k_episodes<POLICY, true>) keep the two
+// planes in device memory instead, for grids whose belief does not fit LDS:
+// same indexing, same lanes, same arithmetic -- see "global placement" below.
 //
 // Every quantity is a function of (seed, episode) and the geometry alone:
 //  * lane t of the 256 owns the padded plane indices i = 1024 j + 4 t + k
@@ -122,6 +125,29 @@ __global__ __launch_bounds__(kBlock) void k_episode_alpha_planes(
                    : rows[(long long)k * ld + (long long)y * g.width + x0 + j];
     }
     store4<false>(out + ((long long)k * g.rows + y) * g.wp + x0, v);
+  }
+}
+
+// ---- padded images of a global launch ---------------------------------------
+// gcode[i] and gb0[i] for the plane index i = (y + 1) * ps + 4 + x: the code
+// and b0 of cell (y, x), +0 / code 0 off the grid (the copies that an LDS
+// workgroup makes for itself, made once per run for all workgroups).  ncode
+// (a multiple of 8, past the last index a window reads) >= nplane.
+__global__ __launch_bounds__(kBlock) void k_episode_pad(Geom g, const uint16_t* __restrict__ code,
+                                                        const float* __restrict__ b0, int ncode,
+                                                        int nplane, uint16_t* __restrict__ gcode,
+                                                        float* __restrict__ gb0) {
+  const int ps = g.wp + 4, prows = g.rows + 2;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < ncode; i += gridDim.x * kBlock) {
+    const int r = i / ps, c = i - r * ps;
+    const int y = r - 1, x = c - 4;
+    const bool in = r < prows && y >= 0 && y < g.rows && x >= 0;
+    uint16_t cv = 0;
+    float bv = 0.0f;
+    if (in && x < g.width) cv = code[(long long)y * g.wp + x];
+    if (in && x < g.wp) bv = b0[(long long)y * g.wp + x];
+    gcode[i] = cv;
+    if (i < nplane) gb0[i] = bv;
   }
 }
 
@@ -521,11 +547,26 @@ __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const Epis
 
 // POLICY: 0 mode, 1 QMDP, 2 the alpha-vector policy (alpha_control), 3 the
 // one-step lookahead over the alpha vectors (lookahead_control).
-template <int POLICY>
+//
+// GLOBAL, the global placement (policies 0..2): the workgroup's two planes are
+// its slice of a.gplanes, the code plane is a.gcode (padded like a plane,
+// built before the launch, read-only here and shared by all workgroups), and
+// step 0 reads the padded b0 image a.gb0 in place of a per-episode copy; the
+// tables, red and asum stay in LDS.  The planes were zeroed when they were
+// allocated and a step stores the interior quads only, so halo rows and x pads
+// hold +0 for good, as the LDS planes' do.  A cell that one wave stores in
+// step k is loaded by other waves of the same workgroup in step k + 1, behind
+// the step's __syncthreads(): workgroup-scope release / acquire, which orders
+// plain vector stores and loads among the waves of one CU (they share its L1;
+// the library is not built in threadgroup-split mode).  The plane loads stay
+// vector loads (every address is the lane's own), nothing crosses workgroups,
+// and there is no agent-scope fence.
+template <int POLICY, bool GLOBAL = false>
 __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
+  static_assert(!GLOBAL || POLICY != 3, "the lookahead runs from LDS planes only");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Geom g = a.g;
-  const EpisodeLds L = episode_lds(g, a.E);
+  const EpisodeLds L = GLOBAL ? episode_lds_global(g, a.E) : episode_lds(g, a.E);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int H = g.rows, W = g.width, wp = g.wp, ps = L.ps;
   const int NP = H * wp;
@@ -535,7 +576,8 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
   float* sCT = lds + L.ct;
   float* sRf = lds + L.rf;
   uint8_t* sCls = reinterpret_cast<uint8_t*>(lds + L.cls);
-  uint16_t* sCode = reinterpret_cast<uint16_t*>(lds + L.code);
+  uint16_t* sCodeL = reinterpret_cast<uint16_t*>(lds + L.code);
+  const uint16_t* sCode = GLOBAL ? a.gcode : sCodeL;
   float* red = lds + L.red;  // [4][9] Q partials | 36: mode v[4] | 40: mode i[4] | 44: max[4]
   int* redi = reinterpret_cast<int*>(red);
   const uint8_t* sLX = reinterpret_cast<const uint8_t*>(sRf + kResLX);
@@ -556,14 +598,19 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       sCls[i] = (uint8_t)cb;
     }
   }
-  const int ncode = L.prows * ps + 8;
-  for (int i = tid; i < ncode; i += kEpThreads) {
-    const int r = i / ps, c = i - r * ps;
-    const int y = r - 1, x = c - 4;
-    uint16_t v = 0;
-    if (r < L.prows && y >= 0 && y < H && x >= 0 && x < W) v = a.code[(long long)y * wp + x];
-    sCode[i] = v;
+  if constexpr (!GLOBAL) {
+    const int ncode = L.prows * ps + 8;
+    for (int i = tid; i < ncode; i += kEpThreads) {
+      const int r = i / ps, c = i - r * ps;
+      const int y = r - 1, x = c - 4;
+      uint16_t v = 0;
+      if (r < L.prows && y >= 0 && y < H && x >= 0 && x < W) v = a.code[(long long)y * wp + x];
+      sCodeL[i] = v;
+    }
   }
+  // global placement: the workgroup's planes (64-bit: workgroups x planes pass 2^31 floats)
+  float* const gp0 = GLOBAL ? a.gplanes + (long long)blockIdx.x * 2 * a.gstride : nullptr;
+  float* const gp1 = GLOBAL ? gp0 + a.gstride : nullptr;
   if constexpr (POLICY == 3) {
     // the L columns transposed, [class][16 z]: a cell's sixteen L_z in one row
     float* ltt = lds + L.total + 2 * kLaSums;
@@ -573,17 +620,21 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
 
   for (int e = blockIdx.x; e < a.episodes; e += gridDim.x) {
     __syncthreads();  // the previous episode's planes are no longer read
-    float* cur = lds + L.b0;
-    float* nxt = lds + L.b1;
-    for (int i = tid; i < planef; i += kEpThreads) {
-      const int r = i / ps, c = i - r * ps;
-      const int y = r - 1, x = c - 4;
-      float v = 0.0f;
-      if (r < L.prows && y >= 0 && y < H && x >= 0 && x < wp) v = a.b0[(long long)y * wp + x];
-      cur[i] = v;
-      nxt[i] = 0.0f;
+    // (global placement: cur is the shared b0 image until the first update,
+    // never written through)
+    float* cur = GLOBAL ? const_cast<float*>(a.gb0) : lds + L.b0;
+    float* nxt = GLOBAL ? gp0 : lds + L.b1;
+    if constexpr (!GLOBAL) {
+      for (int i = tid; i < planef; i += kEpThreads) {
+        const int r = i / ps, c = i - r * ps;
+        const int y = r - 1, x = c - 4;
+        float v = 0.0f;
+        if (r < L.prows && y >= 0 && y < H && x >= 0 && x < wp) v = a.b0[(long long)y * wp + x];
+        cur[i] = v;
+        nxt[i] = 0.0f;
+      }
+      __syncthreads();
     }
-    __syncthreads();
 
     const unsigned long long key = mix64(a.seed + kGolden * (unsigned long long)(e + 1));
     const int s0 = a.start[e];
@@ -755,7 +806,10 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       if (lane == 0) red[44 + wave] = m;
       __syncthreads();
       m = fmaxf(fmaxf(red[44], red[45]), fmaxf(red[46], red[47]));
-      {
+      if constexpr (GLOBAL) {
+        cur = nxt;  // gp0, gp1, gp0, ...: the b0 image is never a target
+        nxt = nxt == gp0 ? gp1 : gp0;
+      } else {
         float* t = cur;
         cur = nxt;
         nxt = t;
@@ -822,7 +876,50 @@ hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const Plan
   return hipGetLastError();
 }
 
-hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups) {
+hipError_t launch_episode_pad(hipStream_t st, const Geom& g, const uint16_t* code,
+                              const float* b0, uint16_t* gcode, float* gb0) {
+  const long long ncode = ep_code_elems(g);
+  const long long nplane = ((long long)g.rows + 2) * (g.wp + 4) + 4;
+  if (ncode > INT_MAX || !code || !b0 || !gcode || !gb0) return hipErrorInvalidValue;
+  const long long nblocks = (ncode + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_episode_pad, dim3((unsigned)(nblocks < 4096 ? nblocks : 4096)),
+                     dim3(kBlock), 0, st, g, code, b0, (int)ncode, (int)nplane, gcode, gb0);
+  return hipGetLastError();
+}
+
+namespace {
+// the global placement's instances: tables, red and asum in LDS, planes in a.gplanes
+hipError_t launch_episodes_global(hipStream_t st, const EpisodeRun& a, int policy,
+                                  int workgroups) {
+  if (policy < 0 || policy > 2 || workgroups < 1 || !a.gplanes || !a.gb0 || !a.gcode ||
+      a.gstride < ((long long)a.g.rows + 2) * (a.g.wp + 4) + 4)
+    return hipErrorInvalidValue;
+  const long long bytes = episode_global_lds_bytes(a.E, policy == 2 ? ep_alpha_floats(a.K) : 0);
+  if (bytes > (long long)kDictLdsMaxBytes) return hipErrorInvalidValue;
+  if (policy == 2) {
+    if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<2, true>), attr);
+    hipLaunchKernelGGL((k_episodes<2, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
+                       st, a);
+  } else if (policy == 1) {
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<1, true>), attr);
+    hipLaunchKernelGGL((k_episodes<1, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
+                       st, a);
+  } else {
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<0, true>), attr);
+    hipLaunchKernelGGL((k_episodes<0, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
+                       st, a);
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
+                           bool global) {
+  if (global) return launch_episodes_global(st, a, policy, workgroups);
   const long long bytes = policy == 3   ? episode_lookahead_lds_bytes(a.g, a.E)
                           : policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K)
                                         : episode_lds_bytes(a.g, a.E);

@@ -27,6 +27,12 @@ STATUS_LOST = 2      # the belief update left no finite positive value
 ALPHA_FIB = 0        # the context's current FIB alphas (K = 9, action of vector k = k)
 ALPHA_PBVI = 1       # the context's PBVI alpha vectors and their actions (K = S)
 _ALPHA_SETS = {"fib": ALPHA_FIB, "pbvi": ALPHA_PBVI}
+
+# where an episode's two belief planes live (include/pp2.h "Placement")
+EPISODES_LDS = 0     # in the workgroup's LDS; a grid that does not fit is refused
+EPISODES_GLOBAL = 1  # in device memory: any grid the context supports
+EPISODES_AUTO = 2    # per launch: LDS if that launch's layout fits, else device memory
+_PLACEMENTS = {"lds": EPISODES_LDS, "global": EPISODES_GLOBAL, "auto": EPISODES_AUTO}
 # ``run``'s names of the one-step lookahead over a set
 _LOOKAHEAD = {"fib-lookahead": "fib", "pbvi-lookahead": "pbvi"}
 
@@ -35,17 +41,36 @@ def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def check_placement(placement) -> int:
+    """The constant of a placement ("lds" | "global" | "auto" or one of the three
+    EPISODES_* constants); raises ValueError on anything else (and never calls
+    the library)."""
+    if isinstance(placement, str):
+        if placement not in _PLACEMENTS:
+            raise ValueError(f"unknown placement {placement!r}")
+        return _PLACEMENTS[placement]
+    if (isinstance(placement, bool) or not isinstance(placement, (int, np.integer))
+            or placement not in (EPISODES_LDS, EPISODES_GLOBAL, EPISODES_AUTO)):
+        raise ValueError(f"unknown placement {placement!r}")
+    return int(placement)
+
+
 class EpisodeBatch:
     """E closed-loop episodes over an unsharded ``GridContext`` with a model,
-    solved (or at least current) MDP values and an active coded model."""
+    solved (or at least current) MDP values and an active coded model.
+    ``placement``: "lds" (the default: the belief planes in the workgroup's
+    LDS, a grid that does not fit is refused), "global" (the planes in device
+    memory, any grid) or "auto" (per launch, LDS where it fits); the results
+    are the same bits from either.  The lookahead runs from LDS only."""
 
     def __init__(self, ctx: GridContext, episodes: int, horizon: int,
-                 record_trace: bool = False):
+                 record_trace: bool = False, placement="lds"):
         episodes, horizon = int(episodes), int(horizon)
         if not 1 <= episodes <= MAX_EPISODES:
             raise ValueError(f"episodes {episodes} outside 1..{MAX_EPISODES}")
         if not 1 <= horizon <= MAX_HORIZON:
             raise ValueError(f"horizon {horizon} outside 1..{MAX_HORIZON}")
+        placement = check_placement(placement)
         self._h = None
         self.ctx = ctx
         self.episodes = episodes
@@ -56,8 +81,12 @@ class EpisodeBatch:
         self.alpha_set = None    # of the last run, if that was an alpha or a lookahead run
         self.lookahead = False   # the last run was a lookahead run
         h = C.c_void_p()
-        call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
-             int(self.record_trace))
+        if placement == EPISODES_LDS:
+            call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
+                 int(self.record_trace))
+        else:
+            call("pp2_episodes_create_placed", C.byref(h), ctx.handle, episodes, horizon,
+                 int(self.record_trace), placement)
         self._h = h
 
     # ------------------------------------------------------------ lifetime
@@ -238,6 +267,14 @@ class EpisodeBatch:
         lds, wgs, th = C.c_int(0), C.c_int(0), C.c_int(0)
         call("pp2_episodes_info", self._h, C.byref(lds), C.byref(wgs), C.byref(th))
         return {"lds_bytes": lds.value, "workgroups": wgs.value, "threads": th.value}
+
+    def placement(self) -> dict:
+        """``requested``: the placement the batch was created with; ``last``:
+        that of the last launch (-1 before any run); ``scratch_bytes``: the
+        device memory held for the global planes (0 until first needed)."""
+        req, last, nbytes = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        call("pp2_episodes_placement", self._h, C.byref(req), C.byref(last), C.byref(nbytes))
+        return {"requested": req.value, "last": last.value, "scratch_bytes": nbytes.value}
 
     def summary(self) -> dict:
         """Success rate, mean steps of the successful episodes (nan if none)

@@ -10,11 +10,18 @@ same process, the host loop the library offered before: BeliefMdpController
 driven by synthetic.closed_loop for mode and QMDP (one belief update and one
 control call per step), and for PBVI one pp2_belief_update, one pp2_belief_get
 and one pp2_pbvi_evaluate per step; 14 episodes of 64 steps each.
+--placement lds | global | auto places the belief planes (include/pp2.h
+"Placement"); --grid HxW times a synthetic.synth_grid(H, W) with cell (0, 0)
+freed and the goal there, as the tests build it, in place of the map -- with
+"global" or "auto" any size, e.g. 256x256, which LDS does not hold.
+--compare-lds also times an LDS batch of the same runs in the same alternating
+rounds and reports the ratio (the price of the memory path, where both fit).
 An episode that reaches the goal stops early, so the device's steps are
 counted from the results; the host loop always runs its 64.  A PBVI entry also
 reports the implied alpha read rate, K * NP * 4 bytes per episode-step.
 
     python tools/episodes_timing.py [--rounds N] [--no-host] [--out FILE]
+                                    [--placement lds|global|auto] [--grid HxW] [--compare-lds]
                                     [--policies mode,qmdp,fib,fibq,pbvi] [--set-size 21,128,500]
         prints one JSON line (and writes it to FILE)
 
@@ -41,15 +48,29 @@ ap.add_argument("--no-host", action="store_true")
 ap.add_argument("--out", default="")
 ap.add_argument("--policies", default="mode,qmdp,fib,fibq,pbvi")
 ap.add_argument("--set-size", default="21", help="PBVI belief set sizes, comma separated")
+ap.add_argument("--placement", default="lds", choices=("lds", "global", "auto"))
+ap.add_argument("--grid", default="", help="HxW: a synthetic grid with goal (0, 0)")
+ap.add_argument("--compare-lds", action="store_true",
+                help="time an LDS batch too, in the same rounds")
 args = ap.parse_args()
 
 E, HORIZON, HOST_EPISODES = 4096, 64, 8
-grid = np.load(os.path.join(ROOT, "tests", "golden", "maps", "sparse_map_100x40.npy"),
-               allow_pickle=False)
-goal = (95, 34)
+if args.grid:
+    try:
+        gh, gw = (int(v) for v in args.grid.lower().split("x"))
+    except ValueError:
+        sys.exit(f"--grid {args.grid!r}: expected HxW")
+    grid = S.synth_grid(gh, gw)
+    grid[0, 0] = 0
+    goal, name = (0, 0), f"synth_{gh}x{gw}"
+else:
+    grid = np.load(os.path.join(ROOT, "tests", "golden", "maps", "sparse_map_100x40.npy"),
+                   allow_pickle=False)
+    goal, name = (95, 34), "sparse_map_100x40"
 b0 = S.uniform_belief(grid)
 starts = S.sample_cells(b0, E, seed=7)
-out = {"map": "sparse_map_100x40", "episodes": E, "horizon": HORIZON, "rounds": args.rounds}
+out = {"map": name, "episodes": E, "horizon": HORIZON, "rounds": args.rounds,
+       "placement": args.placement}
 policies = [p for p in args.policies.split(",") if p]
 for p in policies:
     if p not in ("mode", "qmdp", "fib", "fibq", "pbvi"):
@@ -103,15 +124,20 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
             return "fib"
         return entry
 
-    with P.EpisodeBatch(ctx, E, HORIZON) as ep:
+    with P.EpisodeBatch(ctx, E, HORIZON, placement=args.placement) as ep:
         out.update(ep.info())
-        dev = {p: {"wall_ms": [], "steps": 0} for p in entries}
+        dev = {p: {"wall_ms": [], "steps": 0, "lds_wall_ms": []} for p in entries}
+        lds_ep = P.EpisodeBatch(ctx, E, HORIZON) if args.compare_lds else None
         host = {p: [] for p in entries}
         if "fibq" in entries:
             fib_sets["fibq"] = -ep.run("qmdp", b0, starts, seed=1).qplanes()
         for p in dev:  # warm-up
             ep.run(prepare(p), b0, starts, seed=1).results()
             dev[p]["info"] = ep.info()
+            if lds_ep is not None:
+                lds_ep.run(prepare(p), b0, starts, seed=1).results()
+            if args.placement != "lds":
+                dev[p]["info"].update(ep.placement())
         for rnd in range(args.rounds):  # alternate, so drift hits all alike
             for p in dev:
                 pol = prepare(p)
@@ -121,6 +147,13 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
                 dev[p]["wall_ms"].append((time.perf_counter() - t) * 1e3)
                 dev[p]["steps"] = int(res["steps"].sum())
                 dev[p]["summary"] = ep.summary()
+                if lds_ep is not None:
+                    t = time.perf_counter()
+                    lds_ep.run(pol, b0, starts, seed=1)
+                    lds_res = lds_ep.results()
+                    dev[p]["lds_wall_ms"].append((time.perf_counter() - t) * 1e3)
+                    if not all(np.array_equal(res[k], lds_res[k]) for k in res):
+                        sys.exit(f"{p}: the two placements disagree")
                 if not args.no_host and pol != "fib":
                     ctl = PbviHostLoop(ctx) if pol == "pbvi" else \
                         P.BeliefMdpController(ctx, policy=p)
@@ -137,6 +170,10 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
                       "us_per_episode_step": stats([x * 1e3 / d["steps"] for x in w], 5),
                       "episodes_per_s": stats([E / (x * 1e-3) for x in w], 0),
                       "summary": d["summary"], "info": d["info"]}
+            if d["lds_wall_ms"]:
+                out[p]["lds_wall_ms"] = stats(d["lds_wall_ms"])
+                out[p]["over_lds"] = round(statistics.median(w)
+                                           / statistics.median(d["lds_wall_ms"]), 3)
             if p.startswith("pbvi_"):
                 nbytes = int(p[5:]) * NP * 4
                 out[p]["alpha_bytes_per_episode_step"] = nbytes
@@ -146,6 +183,8 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
                 out[p]["host_loop_us_per_episode_step"] = stats(host[p], 2)
                 out[p]["host_loop_over_device"] = round(
                     statistics.median(host[p]) / out[p]["us_per_episode_step"]["median"], 1)
+        if lds_ep is not None:
+            lds_ep.close()
 line = json.dumps(out)
 print(line)
 if args.out:
