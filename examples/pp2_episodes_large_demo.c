@@ -6,6 +6,10 @@
  * with PP2_EPISODES_AUTO -- which keeps the belief planes of such a grid in
  * device memory -- under the belief-mode policy, the QMDP policy and the
  * FIB-greedy policy: the same robots, seed and cost scale, each in one launch.
+ * Then the one-step lookahead over the FIB alphas, the reference POMDP node's
+ * policy, on the first LOOK_EPISODES of the same robots (its step costs 144
+ * dots per alpha vector, so the batch is smaller):
+ * pp2_episodes_run_lookahead_placed follows the placement to device memory.
  * Prints success rate, mean steps to the goal and mean discounted cost.
  * pp2_episodes_create refuses this grid (PP2_EINVAL); that is shown first.
  * Plain C99, linked against libpp2_hip.so.
@@ -28,6 +32,24 @@
   } while (0)
 
 enum { H = 256, W = 256, EPISODES = 1024, HORIZON = 96, FIB_SWEEPS = 30, GX = 200, GY = 180 };
+enum { LOOK_EPISODES = 512 };
+
+/* one row of the table: the first n episodes' results */
+static int report(const char* name, int n, const int32_t* steps, const uint8_t* status,
+                  const float* cost) {
+  int reached = 0, lost = 0;
+  double sum_steps = 0.0, sum_cost = 0.0;
+  for (int e = 0; e < n; ++e) {
+    if (status[e] > 2 || steps[e] < 0 || steps[e] > HORIZON) return 3;
+    if (status[e] == 1) { ++reached; sum_steps += steps[e]; }
+    lost += status[e] == 2;
+    sum_cost += cost[e];
+  }
+  printf("  %s policy: success rate %.3f, mean steps to the goal %.1f, mean discounted cost "
+         "%.3f, beliefs lost %d\n", name, (double)reached / n,
+         reached ? sum_steps / reached : 0.0, sum_cost / n, lost);
+  return 0;
+}
 
 /* a small linear congruential generator: the map is the program's own */
 static uint32_t lcg(uint32_t* s) {
@@ -97,18 +119,29 @@ int main(void) {
              "of %d threads, %d B of LDS each, planes in %.1f MiB of device memory\n", sweeps,
              FIB_SWEEPS, EPISODES, HORIZON, wgs, threads, lds, (double)scratch / (1024.0 * 1024.0));
     }
-    int reached = 0, lost = 0;
-    double sum_steps = 0.0, sum_cost = 0.0;
-    for (int e = 0; e < EPISODES; ++e) {
-      if (status[e] > 2 || steps[e] < 0 || steps[e] > HORIZON) return 3;
-      if (status[e] == 1) { ++reached; sum_steps += steps[e]; }
-      lost += status[e] == 2;
-      sum_cost += cost[e];
-    }
-    printf("  %s policy: success rate %.3f, mean steps to the goal %.1f, mean discounted cost "
-           "%.3f, beliefs lost %d\n", names[p], (double)reached / EPISODES,
-           reached ? sum_steps / reached : 0.0, sum_cost / EPISODES, lost);
+    if (report(names[p], EPISODES, steps, status, cost)) return 3;
+    if (p == 2 && report("FIB-greedy (the lookahead's episodes)", LOOK_EPISODES, steps, status, cost))
+      return 3;
   }
+  CHECK(pp2_episodes_destroy(ep));
+  /* the one-step lookahead over the same alphas: episode e of a batch depends
+   * on (seed, e) alone, so these are the first LOOK_EPISODES robots again.
+   * pp2_episodes_run_lookahead would refuse this batch (it runs from LDS planes
+   * only); the placed call follows the placement. */
+  ep = NULL;
+  CHECK(pp2_episodes_create_placed(&ep, ctx, LOOK_EPISODES, HORIZON, 0, PP2_EPISODES_AUTO));
+  if (pp2_episodes_run_lookahead(ep, PP2_ALPHA_FIB, 2024, b0, start) != PP2_EINVAL) return 3;
+  CHECK(pp2_episodes_run_lookahead_placed(ep, PP2_ALPHA_FIB, 2024, b0, start));
+  CHECK(pp2_episodes_results(ep, steps, status, cost, NULL));
+  {
+    int lds = 0, wgs = 0, threads = 0, last = -1;
+    CHECK(pp2_episodes_info(ep, &lds, &wgs, &threads));
+    CHECK(pp2_episodes_placement(ep, NULL, &last, NULL));
+    if (last != PP2_EPISODES_GLOBAL) return 3;
+    printf("  lookahead: %d episodes x %d steps, %d workgroups of %d threads, %d B of LDS each\n",
+           LOOK_EPISODES, HORIZON, wgs, threads, lds);
+  }
+  if (report("FIB-lookahead", LOOK_EPISODES, steps, status, cost)) return 3;
   CHECK(pp2_episodes_destroy(ep));
   CHECK(pp2_destroy(ctx));
   return 0;

@@ -533,8 +533,12 @@ int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
  * of b0 and one padded uint16 code plane, both rebuilt by every such run and
  * shared by all workgroups.  Workgroups of such a launch = min(episodes,
  * CUs x 4, what 1 GiB of scratch holds), at least 1.  MODE, QMDP and alpha
- * runs (FIB, and PBVI with any K <= 4096) take either placement; the
- * lookahead runs from LDS only.
+ * runs (FIB, and PBVI with any K <= 4096) take either placement, and so does
+ * the lookahead through pp2_episodes_run_lookahead_placed (a device-memory
+ * lookahead launch has min(episodes, workgroups the scratch holds, CUs x 2)
+ * workgroups, what its registers admit); the older entry
+ * pp2_episodes_run_lookahead keeps its contract and runs from LDS planes or
+ * not at all.
  *
  * Episode e: true cell s = start_cells[e] (y*W + x), stored belief b = b0,
  * cost G = +0, discount d = 1.  If s is the goal: steps 0, status 1, belief
@@ -666,8 +670,8 @@ int pp2_episodes_get_q(pp2_episodes* ep, float* Q);
 /* LDS bytes per workgroup, workgroups and threads per workgroup of the last
  * launch (before any run: of a MODE / QMDP launch; an alpha launch adds its
  * scratch for K != 9, a lookahead launch its own; a device-memory launch
- * keeps only the tables and reduction scratch in LDS and reports that, and
- * its own workgroups) */
+ * keeps only the tables, the reduction scratch and that launch's alpha or
+ * lookahead scratch in LDS and reports that, and its own workgroups) */
 int pp2_episodes_info(pp2_episodes* ep, int* lds_bytes, int* workgroups, int* threads);
 #define PP2_ALPHA_FIB  0   /* the context's current FIB alphas: K = 9, action of vector k = k */
 #define PP2_ALPHA_PBVI 1   /* the context's PBVI alpha vectors and their actions: K = S */
@@ -700,6 +704,24 @@ int pp2_episodes_get_alpha(pp2_episodes* ep, int* count, float* alphas, uint8_t*
  * pp2_episodes_info reports the lookahead launch (its scratch added). */
 int pp2_episodes_run_lookahead(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
                                const int32_t* start_cells);
+/* pp2_episodes_run_lookahead following the batch's placement ("Placement"
+ * above) the way every other run does: the same arithmetic ("Lookahead
+ * runs"), arguments, checks, statuses and asynchrony, the same bits.  A
+ * PP2_EPISODES_LDS batch runs it from LDS exactly as the call above (PP2_EINVAL
+ * if the layout with the lookahead scratch does not fit); a
+ * PP2_EPISODES_GLOBAL batch always runs it from device memory; a
+ * PP2_EPISODES_AUTO batch from LDS if the lookahead layout fits, else from
+ * device memory.  A device-memory launch keeps the tables, the reduction
+ * scratch and the lookahead scratch (4096 bytes) in LDS, uses the batch's
+ * scratch (allocated at the first launch that needs it: PP2_ENOMEM if that
+ * fails, the batch stays usable) and min(episodes, workgroups that scratch
+ * holds, CUs x 2) workgroups; pp2_episodes_placement then reports last =
+ * PP2_EPISODES_GLOBAL and pp2_episodes_info that launch.  Afterwards
+ * pp2_episodes_trace, pp2_episodes_trace_lookahead, pp2_episodes_get_alpha,
+ * pp2_episodes_get_belief and pp2_episodes_results behave as after the call
+ * above. */
+int pp2_episodes_run_lookahead_placed(pp2_episodes* ep, int alpha_set, uint64_t seed,
+                                      const float* b0, const int32_t* start_cells);
 /* The last lookahead run's trace, any may be NULL: q and rewards
  * [horizon][episodes][9] (Q_u, rew[u]); leaf_max and leaf_index
  * [horizon][episodes][9][16] (M_uz, i_uz).  Steps not taken hold 0, 0, 0, -1.

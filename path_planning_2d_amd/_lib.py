@@ -126,6 +126,8 @@ SIGNATURES = {
     "pp2_episodes_trace_alpha": [_vp, C.POINTER(C.c_int32), _f32p],
     "pp2_episodes_get_alpha": [_vp, C.POINTER(C.c_int), _f32p, _u8p],
     "pp2_episodes_run_lookahead": [_vp, C.c_int, C.c_uint64, _f32p, C.POINTER(C.c_int32)],
+    "pp2_episodes_run_lookahead_placed": [_vp, C.c_int, C.c_uint64, _f32p,
+                                          C.POINTER(C.c_int32)],
     "pp2_episodes_trace_lookahead": [_vp, _f32p, _f32p, _f32p, C.POINTER(C.c_int32)],
     "pp2_shard_group_create": [C.POINTER(_vp), C.POINTER(_vp), C.c_int],
     "pp2_shard_group_destroy": [_vp],

@@ -7,7 +7,9 @@
 // A batch created with pp2_episodes_create_placed may keep the belief planes in
 // device memory instead of LDS (pp2_episodes.h "Placement"): such a launch is
 // preceded by the kernel that pads the code plane and b0, and works in a
-// scratch allocated at the first such launch.
+// scratch allocated at the first such launch.  Every policy follows the
+// placement; the lookahead does so through pp2_episodes_run_lookahead_placed,
+// while pp2_episodes_run_lookahead keeps its contract (LDS planes or PP2_EINVAL).
 #include <cstring>
 #include <vector>
 
@@ -157,12 +159,23 @@ ScratchPlan scratch_plan(const pp2_ctx* c, int episodes) {
   p.bytes = p.workgroups * p.per_wg + p.shared;
   return p;
 }
+// Workgroups of a global lookahead launch: the instance's registers admit
+// kEpGlobalLookaheadPerCu per CU, and the launch uses the first plane pairs of
+// the batch's scratch (scratch_wgs of them, sized for the other instances).
+int global_lookahead_workgroups(const pp2_ctx* c, int episodes, int scratch_wgs) {
+  long long w = (long long)(c->ncus > 0 ? c->ncus : 256) * pp2::kEpGlobalLookaheadPerCu;
+  w = w < episodes ? w : episodes;
+  w = w < scratch_wgs ? w : scratch_wgs;
+  return (int)(w < 1 ? 1 : w);
+}
 
 // One run.  policy: PP2_CONTROL_MODE / PP2_CONTROL_QMDP, or kPolicyAlpha /
 // kPolicyLookahead with alpha_set PP2_ALPHA_FIB / PP2_ALPHA_PBVI (all checked
-// by the callers).
+// by the callers).  lds_only_lookahead: pp2_episodes_run_lookahead's contract,
+// which refuses a lookahead launch that would not run from LDS planes;
+// pp2_episodes_run_lookahead_placed follows the placement as every other run.
 int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const float* b0,
-             const int32_t* start_cells) {
+             const int32_t* start_cells, bool lds_only_lookahead = false) {
   pp2_ctx* c = ep->ctx;
   const bool look = policy == kPolicyLookahead;
   const bool alpha = policy == kPolicyAlpha || look;  // reads an alpha set
@@ -192,14 +205,16 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   const bool fits = lds <= (long long)pp2::kDictLdsMaxBytes;
   const bool global = ep->placement == PP2_EPISODES_GLOBAL ||
                       (ep->placement == PP2_EPISODES_AUTO && !fits);
-  if (look && ep->placement == PP2_EPISODES_GLOBAL)
+  if (lds_only_lookahead && ep->placement == PP2_EPISODES_GLOBAL)
     return set_err(PP2_EINVAL,
-                   "the lookahead runs from LDS planes only: the batch was created with "
-                   "PP2_EPISODES_GLOBAL");
-  if (look && global)
+                   "pp2_episodes_run_lookahead runs from LDS planes only: the batch was created "
+                   "with PP2_EPISODES_GLOBAL (pp2_episodes_run_lookahead_placed follows the "
+                   "placement)");
+  if (lds_only_lookahead && global)
     return set_err(PP2_EINVAL,
-                   "the lookahead runs from LDS planes only, and a %d x %d belief with the "
-                   "lookahead scratch needs %lld bytes of LDS per episode (at most %zu fit)",
+                   "pp2_episodes_run_lookahead runs from LDS planes only, and a %d x %d belief "
+                   "with the lookahead scratch needs %lld bytes of LDS per episode (at most %zu "
+                   "fit; pp2_episodes_run_lookahead_placed follows the placement)",
                    W, H, lds, pp2::kDictLdsMaxBytes);
   if (!global && !fits)  // (the LDS placement's alpha and lookahead layouts)
     return set_err(PP2_EINVAL,
@@ -208,8 +223,9 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
                    W, H, look ? "lookahead" : "alpha", lds, pp2::kDictLdsMaxBytes);
   ScratchPlan plan{};
   if (global) {
-    lds = pp2::episode_global_lds_bytes(c->dict_n,
-                                        policy == kPolicyAlpha ? pp2::ep_alpha_floats(K) : 0);
+    lds = pp2::episode_global_lds_bytes(c->dict_n, look    ? pp2::ep_lookahead_floats()
+                                                   : alpha ? pp2::ep_alpha_floats(K)
+                                                           : 0);
     if (lds > (long long)pp2::kDictLdsMaxBytes)
       return set_err(PP2_EINVAL, "the tables of %d dictionary entries need %lld bytes of LDS",
                      c->dict_n, lds);
@@ -276,10 +292,11 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     }
   }
   ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
-  ep->workgroups = global  ? ep->scratch_wgs
-                   : look  ? episode_workgroups(c, E, lds, kLookaheadPerCu)
-                   : alpha ? episode_workgroups(c, E, lds)
-                           : ep->base_workgroups;
+  ep->workgroups = global && look ? global_lookahead_workgroups(c, E, ep->scratch_wgs)
+                   : global       ? ep->scratch_wgs
+                   : look         ? episode_workgroups(c, E, lds, kLookaheadPerCu)
+                   : alpha        ? episode_workgroups(c, E, lds)
+                                  : ep->base_workgroups;
   for (int y = 0; y < H; ++y)
     std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
   std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
@@ -487,6 +504,15 @@ int pp2_episodes_run_alpha(pp2_episodes* ep, int alpha_set, uint64_t seed, const
 
 int pp2_episodes_run_lookahead(pp2_episodes* ep, int alpha_set, uint64_t seed, const float* b0,
                                const int32_t* start_cells) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (!b0 || !start_cells) return set_err(PP2_EINVAL, "null argument");
+  if (alpha_set != PP2_ALPHA_FIB && alpha_set != PP2_ALPHA_PBVI)
+    return set_err(PP2_EINVAL, "unknown alpha set %d", alpha_set);
+  return run_impl(ep, kPolicyLookahead, alpha_set, seed, b0, start_cells, true);
+}
+
+int pp2_episodes_run_lookahead_placed(pp2_episodes* ep, int alpha_set, uint64_t seed,
+                                      const float* b0, const int32_t* start_cells) {
   if (!ep) return set_err(PP2_EINVAL, "null episode batch");
   if (!b0 || !start_cells) return set_err(PP2_EINVAL, "null argument");
   if (alpha_set != PP2_ALPHA_FIB && alpha_set != PP2_ALPHA_PBVI)

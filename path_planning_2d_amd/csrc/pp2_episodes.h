@@ -27,9 +27,10 @@
 //
 // Placement.  The above is the LDS placement (PP2_EPISODES_LDS), which admits
 // the grids whose planes fit kDictLdsMaxBytes.  The global placement
-// (PP2_EPISODES_GLOBAL; k_episodes<POLICY, true>, policies 0..2) keeps the
-// tables, red and asum in LDS -- ct | rf | cls | red | asum, episode_lds_global
-// -- and the planes in one device allocation of the batch (the scratch):
+// (PP2_EPISODES_GLOBAL; k_episodes<POLICY, true>, all four policies) keeps the
+// tables, red and asum (the lookahead: sums and ltt in its place) in LDS --
+// ct | rf | cls | red | asum, episode_lds_global -- and the planes in one
+// device allocation of the batch (the scratch):
 //   planes  [workgroups][2] belief planes of ep_plane_stride floats, the LDS
 //           planes' own indexing; zeroed once when allocated: a step writes the
 //           interior quads only, so halo rows and x pads stay zero
@@ -43,7 +44,11 @@
 // workgroup is one wave per SIMD, and the three global instances take 121
 // (MODE), 127 (QMDP) and 118 (alpha) VGPRs, which is 4 waves per SIMD
 // (512 / 128): kEpGlobalPerCu = 4.  More workgroups than that would only queue
-// behind the resident ones and widen the scratch.
+// behind the resident ones and widen the scratch.  The global lookahead
+// instance takes 225 VGPRs, 2 waves per SIMD: kEpGlobalLookaheadPerCu = 2, and
+// its launch is min(episodes, workgroups the scratch holds, CUs x 2) workgroups
+// on the first plane pairs of the same scratch (the b0 image and the code plane
+// stay behind all of the scratch's pairs, wherever they were first placed).
 #pragma once
 #include "pp2_internal.h"
 
@@ -55,6 +60,9 @@ constexpr int kEpMaxPerCu = 8;  // workgroups per CU the grid is sized for
 // global placement: workgroups per CU by the instances' VGPRs (see above), and
 // the cap on the scratch that holds every workgroup's two planes
 constexpr int kEpGlobalPerCu = 4;
+// ... of the global lookahead instance k_episodes<3, true>: 225 VGPRs, no
+// private scratch, 2 waves per SIMD (the LDS instance: 220, also 2)
+constexpr int kEpGlobalLookaheadPerCu = 2;
 constexpr long long kEpScratchCapBytes = 1LL << 30;
 // The alpha-vector policy (k_episodes<2>): K vectors in blocks of
 // kEpAlphaBlock accumulators, their per-wave sums staged per chunk of
@@ -116,7 +124,8 @@ __host__ __device__ inline EpisodeLds episode_lds_global(const Geom& g, int E) {
   l.total = l.red + kEpRedFloats;
   return l;
 }
-// ... its bytes (alpha_floats: ep_alpha_floats(K) of an alpha run, else 0)
+// ... its bytes (alpha_floats: ep_alpha_floats(K) of an alpha run,
+// ep_lookahead_floats() of a lookahead run, else 0)
 inline long long episode_global_lds_bytes(int E, int alpha_floats) {
   return 4LL * (ep_table_floats(E) + kEpRedFloats + alpha_floats);
 }
@@ -204,8 +213,9 @@ hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const Plan
 // policy: PP2_CONTROL_MODE (0), PP2_CONTROL_QMDP (1), 2, the alpha-vector
 // policy over a.alpha, or 3, the one-step lookahead over a.alpha and
 // a.rplanes.  hipErrorInvalidValue when the workgroup's LDS does not fit.
-// global: the global-placement instance (policies 0..2; a.gplanes, a.gb0 and
-// a.gcode set, built by launch_episode_pad on the same stream).
+// global: the global-placement instance (a.gplanes, a.gb0 and a.gcode set,
+// built by launch_episode_pad on the same stream; workgroups at most the
+// plane pairs a.gplanes holds).
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
                            bool global = false);
 // The padded images of a global launch: gcode[(y + 1) * ps + 4 + x] = code of

@@ -446,10 +446,12 @@ __device__ __forceinline__ void lookahead_block(const EpisodeRun& a, const float
 //    the quads of z = l % 16 in ascending k into its running (max, index).
 //    Two buffers, as alpha_control's chunks.
 //  * S_u from the sixteen lanes' maxima in ascending z (lane reads).
+// sCode: the instance's code plane (LDS, or a.gcode of a global launch); cur
+// and pred are LDS planes or the workgroup's device-memory planes alike.
 __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const EpisodeLds& L,
-                                                 float* lds, const float* cur, float* pred,
-                                                 float sc, int k, int e, int qy0, int qx0,
-                                                 int qdy, int qdx) {
+                                                 float* lds, const uint16_t* sCode,
+                                                 const float* cur, float* pred, float sc, int k,
+                                                 int e, int qy0, int qx0, int qdy, int qdx) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int W = a.g.width, wp = a.g.wp, ps = L.ps, K = a.K;
   const int NP = a.g.rows * wp;
@@ -459,7 +461,6 @@ __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const Epis
   const float* ltt = sums + 2 * kLaSums;
   const float* sRf = lds + L.rf;
   const uint8_t* sCls = reinterpret_cast<const uint8_t*>(lds + L.cls);
-  const uint16_t* sCode = reinterpret_cast<const uint16_t*>(lds + L.code);
   const uint8_t* sLX = reinterpret_cast<const uint8_t*>(sRf + kResLX);
   const float* sQR = sRf + kResQR;
   int best = 0, buf = 0;
@@ -548,7 +549,7 @@ __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const Epis
 // POLICY: 0 mode, 1 QMDP, 2 the alpha-vector policy (alpha_control), 3 the
 // one-step lookahead over the alpha vectors (lookahead_control).
 //
-// GLOBAL, the global placement (policies 0..2): the workgroup's two planes are
+// GLOBAL, the global placement (all four policies): the workgroup's two planes are
 // its slice of a.gplanes, the code plane is a.gcode (padded like a plane,
 // built before the launch, read-only here and shared by all workgroups), and
 // step 0 reads the padded b0 image a.gb0 in place of a per-episode copy; the
@@ -561,9 +562,29 @@ __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const Epis
 // the library is not built in threadgroup-split mode).  The plane loads stay
 // vector loads (every address is the lane's own), nothing crosses workgroups,
 // and there is no agent-scope fence.
+//
+// The lookahead on global planes (k_episodes<3, true>): sums and ltt sit behind
+// episode_lds_global's total, and pred is nxt, the idle plane, as in LDS -- the
+// workgroup's plane 0 at step 0 (cur is the shared b0 image, never written),
+// afterwards the other of its two planes.  What the LDS instance relies on
+// holds here for the same reasons:
+//  * the gather stores exactly the quads step 5 stores (PP2_EP_QUADS, cell
+//    (y, x0) at (y + 1) * ps + 4 + x0), so the halo rows and x pads of a plane
+//    zeroed at allocation stay +0 for the batch's life -- for step 5's window,
+//    the workgroup's next episode and later runs of any policy on the batch;
+//  * cells x >= W of a quad are stored as +0, as step 5 stores them: whichever
+//    of the two wrote a plane last, its cells W <= x < wp hold +0;
+//  * a lane reads back only the quads it stored itself: the store and the
+//    load are plain C++ accesses of one thread to one address, which the
+//    compiler keeps in order (vector store, then vector load behind its
+//    s_waitcnt), so no barrier lies between the gather and the dots;
+//  * pred is written only while no wave reads it: every wave's window reads
+//    of that plane (it was cur one step earlier) precede step 5's barrier of
+//    that step, and the episode loop's barrier covers the final belief store.
+// The step's two __syncthreads() (and one per block of the dots, on LDS sums)
+// remain the only synchronisation.
 template <int POLICY, bool GLOBAL = false>
 __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
-  static_assert(!GLOBAL || POLICY != 3, "the lookahead runs from LDS planes only");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Geom g = a.g;
   const EpisodeLds L = GLOBAL ? episode_lds_global(g, a.E) : episode_lds(g, a.E);
@@ -652,7 +673,7 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       // 1. control: the lane's partials
       int u = 0, mcell = 0;
       if constexpr (POLICY == 3) {
-        u = lookahead_control(a, L, lds, cur, nxt, sc, k, e, qy0, qx0, qdy, qdx);
+        u = lookahead_control(a, L, lds, sCode, cur, nxt, sc, k, e, qy0, qx0, qdy, qdx);
       } else if constexpr (POLICY == 2) {
         u = alpha_control(a, L, lds, cur, sc, k, e, qy0, qx0, qdy, qdx);
       } else {
@@ -891,12 +912,20 @@ namespace {
 // the global placement's instances: tables, red and asum in LDS, planes in a.gplanes
 hipError_t launch_episodes_global(hipStream_t st, const EpisodeRun& a, int policy,
                                   int workgroups) {
-  if (policy < 0 || policy > 2 || workgroups < 1 || !a.gplanes || !a.gb0 || !a.gcode ||
+  if (policy < 0 || policy > 3 || workgroups < 1 || !a.gplanes || !a.gb0 || !a.gcode ||
       a.gstride < ((long long)a.g.rows + 2) * (a.g.wp + 4) + 4)
     return hipErrorInvalidValue;
-  const long long bytes = episode_global_lds_bytes(a.E, policy == 2 ? ep_alpha_floats(a.K) : 0);
+  const long long bytes = episode_global_lds_bytes(a.E, policy == 3   ? ep_lookahead_floats()
+                                                        : policy == 2 ? ep_alpha_floats(a.K)
+                                                                      : 0);
   if (bytes > (long long)kDictLdsMaxBytes) return hipErrorInvalidValue;
-  if (policy == 2) {
+  if (policy == 3) {
+    if (!a.alpha || !a.rplanes || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
+    static unsigned long long attr = 0;
+    allow_lds(reinterpret_cast<const void*>(&k_episodes<3, true>), attr);
+    hipLaunchKernelGGL((k_episodes<3, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
+                       st, a);
+  } else if (policy == 2) {
     if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
     static unsigned long long attr = 0;
     allow_lds(reinterpret_cast<const void*>(&k_episodes<2, true>), attr);

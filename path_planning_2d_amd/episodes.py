@@ -41,6 +41,12 @@ def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _check_placed(placed) -> bool:
+    if not isinstance(placed, bool):
+        raise ValueError(f"placed must be a bool, not {placed!r}")
+    return placed
+
+
 def check_placement(placement) -> int:
     """The constant of a placement ("lds" | "global" | "auto" or one of the three
     EPISODES_* constants); raises ValueError on anything else (and never calls
@@ -61,7 +67,11 @@ class EpisodeBatch:
     ``placement``: "lds" (the default: the belief planes in the workgroup's
     LDS, a grid that does not fit is refused), "global" (the planes in device
     memory, any grid) or "auto" (per launch, LDS where it fits); the results
-    are the same bits from either.  The lookahead runs from LDS only."""
+    are the same bits from either.  Every policy follows the placement; the
+    lookahead does so with ``placed=True`` (``run_lookahead`` / ``run``), which
+    calls ``pp2_episodes_run_lookahead_placed``.  Without it the lookahead keeps
+    the older entry's contract: it runs from LDS planes, and a "global" batch
+    or an "auto" batch whose lookahead layout does not fit LDS refuses it."""
 
     def __init__(self, ctx: GridContext, episodes: int, horizon: int,
                  record_trace: bool = False, placement="lds"):
@@ -135,16 +145,18 @@ class EpisodeBatch:
             raise ValueError("seed must fit 64 bits")
         return int(policy), b0, np.ascontiguousarray(start, np.int32), seed
 
-    def run(self, policy, b0, start_cells, seed: int = 0):
+    def run(self, policy, b0, start_cells, seed: int = 0, placed: bool = False):
         """Enqueue one batch: every episode starts from belief ``b0`` with its
         true robot at ``start_cells[e]`` (``y * W + x``).  ``policy``: "mode",
         "qmdp" (or CONTROL_MODE / CONTROL_QMDP), "fib" / "pbvi", which are
         ``run_alpha``, or "fib-lookahead" / "pbvi-lookahead", which are
-        ``run_lookahead``.  Asynchronous."""
+        ``run_lookahead`` (``placed`` as there; the other policies follow the
+        placement anyway, so it changes nothing for them).  Asynchronous."""
+        placed = _check_placed(placed)
         if isinstance(policy, str) and policy in _ALPHA_SETS:
             return self.run_alpha(policy, b0, start_cells, seed)
         if isinstance(policy, str) and policy in _LOOKAHEAD:
-            return self.run_lookahead(_LOOKAHEAD[policy], b0, start_cells, seed)
+            return self.run_lookahead(_LOOKAHEAD[policy], b0, start_cells, seed, placed)
         policy, b0, start, seed = self.check_run_args(self.cells, self.episodes, policy, b0,
                                                       start_cells, seed)
         call("pp2_episodes_run", self._h, policy, C.c_uint64(seed), _f32(b0), _i32(start))
@@ -180,15 +192,20 @@ class EpisodeBatch:
         self.lookahead = False
         return self
 
-    def run_lookahead(self, alpha_set, b0, start_cells, seed: int = 0):
+    def run_lookahead(self, alpha_set, b0, start_cells, seed: int = 0, placed: bool = False):
         """``run`` under the one-step lookahead policy over an alpha-vector set
         ("fib" / "pbvi", as ``run_alpha``): the action with the largest
         Q(b, u) = <b, R_u> + gamma * sum_z max_k <L_z . T_u^T b, alpha_k>, the
         reference POMDP node's tree at depth 1 with exact observation
-        weights.  Asynchronous."""
+        weights.  ``placed=True`` follows the batch's placement as every other
+        run does (``pp2_episodes_run_lookahead_placed``: device-memory planes
+        on a "global" batch and on an "auto" batch whose lookahead layout does
+        not fit LDS, the same bits); the default runs from LDS planes or raises
+        ``Pp2Error`` (PP2_EINVAL).  Asynchronous."""
+        placed = _check_placed(placed)
         alpha_set, b0, start, seed = self._check_alpha_args(alpha_set, b0, start_cells, seed)
-        call("pp2_episodes_run_lookahead", self._h, alpha_set, C.c_uint64(seed), _f32(b0),
-             _i32(start))
+        call("pp2_episodes_run_lookahead_placed" if placed else "pp2_episodes_run_lookahead",
+             self._h, alpha_set, C.c_uint64(seed), _f32(b0), _i32(start))
         self.policy = None
         self.alpha_set = alpha_set
         self.lookahead = True

@@ -19,10 +19,17 @@ rounds and reports the ratio (the price of the memory path, where both fit).
 An episode that reaches the goal stops early, so the device's steps are
 counted from the results; the host loop always runs its 64.  A PBVI entry also
 reports the implied alpha read rate, K * NP * 4 bytes per episode-step.
+--policies also takes "fib-lookahead" and "pbvi-lookahead" (the latter an entry
+per --set-size), the one-step lookahead over the set; they have no host loop.
+With --placement global | auto they go through the call that follows the
+placement (``placed=True``); the --compare-lds batch runs the plain call.
+--episodes / --horizon replace E = 4096 and horizon 64 (a lookahead step on a
+large grid costs milliseconds per workgroup).
 
     python tools/episodes_timing.py [--rounds N] [--no-host] [--out FILE]
                                     [--placement lds|global|auto] [--grid HxW] [--compare-lds]
-                                    [--policies mode,qmdp,fib,fibq,pbvi] [--set-size 21,128,500]
+                                    [--policies mode,qmdp,fib,fibq,pbvi,fib-lookahead,pbvi-lookahead]
+                                    [--set-size 21,128,500] [--episodes E] [--horizon N]
         prints one JSON line (and writes it to FILE)
 
 Kernel time comes from a separate run under
@@ -52,9 +59,15 @@ ap.add_argument("--placement", default="lds", choices=("lds", "global", "auto"))
 ap.add_argument("--grid", default="", help="HxW: a synthetic grid with goal (0, 0)")
 ap.add_argument("--compare-lds", action="store_true",
                 help="time an LDS batch too, in the same rounds")
+ap.add_argument("--episodes", type=int, default=4096)
+ap.add_argument("--horizon", type=int, default=64)
 args = ap.parse_args()
 
-E, HORIZON, HOST_EPISODES = 4096, 64, 8
+E, HORIZON, HOST_EPISODES = args.episodes, args.horizon, 8
+LOOKAHEAD = ("fib-lookahead", "pbvi-lookahead")
+# a lookahead run follows the placement through the placed call; on an LDS
+# batch it is the old call, which the tool then keeps
+PLACED = args.placement != "lds"
 if args.grid:
     try:
         gh, gw = (int(v) for v in args.grid.lower().split("x"))
@@ -73,11 +86,13 @@ out = {"map": name, "episodes": E, "horizon": HORIZON, "rounds": args.rounds,
        "placement": args.placement}
 policies = [p for p in args.policies.split(",") if p]
 for p in policies:
-    if p not in ("mode", "qmdp", "fib", "fibq", "pbvi"):
+    if p not in ("mode", "qmdp", "fib", "fibq", "pbvi") + LOOKAHEAD:
         sys.exit(f"unknown policy {p!r}")
-sizes = [int(s) for s in args.set_size.split(",") if s] if "pbvi" in policies else []
-# the entries timed: a PBVI entry per set size
-entries = [p for p in policies if p != "pbvi"] + [f"pbvi_{s}" for s in sizes]
+PBVI = ("pbvi", "pbvi-lookahead")
+sizes = [int(s) for s in args.set_size.split(",") if s] if set(PBVI) & set(policies) else []
+# the entries timed: a PBVI (or PBVI-lookahead) entry per set size
+entries = [p for p in policies if p not in PBVI] + \
+    [f"{p}_{s}" for p in PBVI if p in policies for s in sizes]
 
 
 def stats(v, nd=3):
@@ -105,9 +120,9 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
     ctx.model_generate()
     out["mdp_sweeps"] = ctx.mdp_solve()[0]
     fib_sets = {}
-    if "fib" in policies:
+    if "fib" in policies or "fib-lookahead" in policies:
         out["fib_sweeps"] = ctx.fib_solve()[0]
-        fib_sets["fib"] = ctx.fib_get()
+        fib_sets["fib"] = fib_sets["fib-lookahead"] = ctx.fib_get()
     sets = {}
     for s in sizes:  # solved once; a round only uploads the set it times
         ctx.pbvi_solve(b0, s)
@@ -116,13 +131,19 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
 
     def prepare(entry):
         """-> the policy to run"""
-        if entry.startswith("pbvi_"):
-            ctx.pbvi_set(*sets[int(entry[5:])])
-            return "pbvi"
+        if entry.startswith(("pbvi_", "pbvi-lookahead_")):
+            pol, size = entry.rsplit("_", 1)
+            ctx.pbvi_set(*sets[int(size)])
+            return pol
         if entry in fib_sets:
             ctx.fib_set(fib_sets[entry])
-            return "fib"
+            return entry if entry in LOOKAHEAD else "fib"
         return entry
+
+    def run(batch, pol, placed):
+        """One run of the policy; ``placed``: a lookahead run through the
+        call that follows the batch's placement."""
+        return batch.run(pol, b0, starts, seed=1, placed=placed and pol in LOOKAHEAD)
 
     with P.EpisodeBatch(ctx, E, HORIZON, placement=args.placement) as ep:
         out.update(ep.info())
@@ -132,29 +153,29 @@ with P.GridContext(grid, goal, gamma=0.95) as ctx:
         if "fibq" in entries:
             fib_sets["fibq"] = -ep.run("qmdp", b0, starts, seed=1).qplanes()
         for p in dev:  # warm-up
-            ep.run(prepare(p), b0, starts, seed=1).results()
+            run(ep, prepare(p), PLACED).results()
             dev[p]["info"] = ep.info()
             if lds_ep is not None:
-                lds_ep.run(prepare(p), b0, starts, seed=1).results()
+                run(lds_ep, prepare(p), False).results()
             if args.placement != "lds":
                 dev[p]["info"].update(ep.placement())
         for rnd in range(args.rounds):  # alternate, so drift hits all alike
             for p in dev:
                 pol = prepare(p)
                 t = time.perf_counter()
-                ep.run(pol, b0, starts, seed=1)
+                run(ep, pol, PLACED)
                 res = ep.results()
                 dev[p]["wall_ms"].append((time.perf_counter() - t) * 1e3)
                 dev[p]["steps"] = int(res["steps"].sum())
                 dev[p]["summary"] = ep.summary()
                 if lds_ep is not None:
                     t = time.perf_counter()
-                    lds_ep.run(pol, b0, starts, seed=1)
+                    run(lds_ep, pol, False)
                     lds_res = lds_ep.results()
                     dev[p]["lds_wall_ms"].append((time.perf_counter() - t) * 1e3)
                     if not all(np.array_equal(res[k], lds_res[k]) for k in res):
                         sys.exit(f"{p}: the two placements disagree")
-                if not args.no_host and pol != "fib":
+                if not args.no_host and pol != "fib" and pol not in LOOKAHEAD:
                     ctl = PbviHostLoop(ctx) if pol == "pbvi" else \
                         P.BeliefMdpController(ctx, policy=p)
                     t = time.perf_counter()
