@@ -67,6 +67,7 @@
 // exits before any global store if it is raised (the host re-runs it too).
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "pp2_coded_dev.h"
 
@@ -512,6 +513,87 @@ __device__ __forceinline__ void row_zero(float (&v)[6]) {
 #pragma unroll
   for (int i = 0; i < 6; ++i) v[i] = 0.0f;
 }
+// The whole-row instance's window rows in one LDS round trip
+// (PP2_RES_WINDOW1; A/B builds: 0 keeps three row_lds pairs).  row_lds per
+// row compiles to a dependent round trip per row: its 2-lane edge read is a
+// save-exec region of its own, the DPP that takes the edge dword as `old`
+// follows it directly, and the scheduler moves no later row's reads across
+// the region -- three drains at the step's top, on every wave at once (all
+// 16 have just left the barrier).  Here every read of the b and J rows that
+// live in LDS is issued first -- the quads (ds_read_b128, rows ty - 1 and
+// ty + 1 under wave-uniform branches), then the six edge dwords -- and the
+// DPP moves (window_row) follow the caller's scheduling barrier, so with the
+// class dwords and the action-0 records before them the step's top is one
+// issue burst and one wait.  An edge wave polls its neighbour's granules
+// between the two: its own rows land under the poll.
+// The edge dwords: 1 -- ONE exec-masked region (lanes 0 / 63), as
+// load_class_rows; 2 -- branch-free: lanes 0..31 read lane 0's dword and lanes
+// 32..63 lane 63's (two addresses, each a broadcast: no bank conflict), the
+// other lanes' copies are unused (a DPP's `old` counts on lanes 0 / 63 only).
+// A row that is not in LDS (in0 / in2 false: a neighbour's, or off the grid)
+// reads row ty's dwords again, unused, instead of a branch inside the region.
+// The edge dwords the first DPPs consume (row ty - 1's, else row ty's) go out
+// last, so that the first wait is the only one (LDS returns in order).
+// (2 by A/B: at or below 1 in every repetition of the 400- and 2000-step launches and
+// of the sweep, profiles/r10/ab_resident_variants.txt)
+#ifndef PP2_RES_WINDOW1
+#define PP2_RES_WINDOW1 2
+#endif
+// (k_sweep_resident's J rows and its action-0 records likewise)
+#ifndef PP2_RES_SWEEP_WINDOW1
+#define PP2_RES_SWEEP_WINDOW1 PP2_RES_WINDOW1
+#endif
+#if PP2_RES_WINDOW1 != 0 || PP2_RES_SWEEP_WINDOW1 != 0
+// NP planes (the loop: b, J; the sweep: J): quads q and edge dwords e of
+// window rows 0 .. 2; p[k] is the lane's quad in row ty of plane k.
+template <int NP>
+struct WinRows {
+  f4a q[NP][3];
+  float e[NP][3];
+};
+template <int MODE, int NP>
+__device__ __forceinline__ void issue_window_rows(const float* const (&p)[NP], int xs, bool in0,
+                                                  bool in2, WinRows<NP>& w) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) w.q[k][1] = *reinterpret_cast<const f4a*>(p[k]);
+  if (in0) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k) w.q[k][0] = *reinterpret_cast<const f4a*>(p[k] - xs);
+  }
+  if (in2) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k) w.q[k][2] = *reinterpret_cast<const f4a*>(p[k] + xs);
+  }
+  const int o0 = in0 ? -xs : 0, o2 = in2 ? xs : 0;
+  // rows 2, 1, then row 0 with plane 0 last
+  auto edges = [&](int eo) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k) w.e[k][2] = p[k][o2 + eo];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) w.e[k][1] = p[k][eo];
+#pragma unroll
+    for (int k = NP - 1; k >= 0; --k) w.e[k][0] = p[k][o0 + eo];
+  };
+  if constexpr (MODE == 1) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) w.e[k][r] = 0.0f;
+    if (lane == 0 || lane == 63) edges(lane == 0 ? -1 : 4);
+  } else {
+    edges(lane < 32 ? -1 - 4 * lane : 4 + 4 * (63 - lane));
+  }
+}
+// window row r from the quads and edge dwords in hand (row_lds's DPP moves)
+__device__ __forceinline__ void window_row(const f4a& m, float e, float (&v)[6]) {
+  v[0] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[3]),
+                                                    0x138, 0xf, 0xf, false));
+  v[1] = m[0]; v[2] = m[1]; v[3] = m[2]; v[4] = m[3];
+  v[5] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[0]),
+                                                    0x130, 0xf, 0xf, false));
+}
+#endif
 
 // Edge-row hand-off by self-tagged words (MI355X_MICROARCH.md § visibility,
 // handoff-1to1: the data is the flag).  Every value handed over -- belief and
@@ -1188,25 +1270,59 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         if (last) coded_sweep_iw_pipe_begin<4, true>(sTC, iwr, rtv, rcost, best, arg);
         else coded_sweep_iw_pipe_begin<4, false>(sTC, iwr, rtv, rcost, best, arg);
       }
-      if (ty > 0) {
-        row_lds(sbuf(0, ci) + (ty - 1) * xs, x0, wb.v[0]);
-        row_lds(sbuf(1, ci) + (ty - 1) * xs, x0, wj.v[0]);
-      } else if (nb_up) {  // the tile above's last row (and the side cells)
-        take(co, true, tile - tc, 1, sd, bit, wb.v[0], wj.v[0], sb, sj);
-      } else {
-        row_zero(wb.v[0]);
-        row_zero(wj.v[0]);
-      }
-      row_lds(sbuf(0, ci) + ty * xs, x0, wb.v[1]);
-      row_lds(sbuf(1, ci) + ty * xs, x0, wj.v[1]);
-      if (ty + 1 < a.rt && y + 1 < rows) {
-        row_lds(sbuf(0, ci) + (ty + 1) * xs, x0, wb.v[2]);
-        row_lds(sbuf(1, ci) + (ty + 1) * xs, x0, wj.v[2]);
-      } else if (nb_dn) {  // the tile below's first row (and the side cells)
-        take(co, true, tile + tc, 0, sd && !nb_up, bit, wb.v[2], wj.v[2], sb, sj);
-      } else {
-        row_zero(wb.v[2]);
-        row_zero(wj.v[2]);
+#if PP2_RES_WINDOW1 != 0
+      if constexpr (kSweepPipe) {
+        // every LDS read of the window rows issued here, behind the class
+        // dwords and the records and before a neighbour's poll; the DPP moves
+        // (window_row) consume them after it
+        const bool in0 = ty > 0, in2 = ty + 1 < a.rt && y + 1 < rows;
+        WinRows<2> wr;
+        const float* const wp2[2] = {sbuf(0, ci) + ty * xs + x0, sbuf(1, ci) + ty * xs + x0};
+        issue_window_rows<PP2_RES_WINDOW1>(wp2, xs, in0, in2, wr);
+        __builtin_amdgcn_sched_barrier(0);
+        if (in0) {
+          window_row(wr.q[0][0], wr.e[0][0], wb.v[0]);
+          window_row(wr.q[1][0], wr.e[1][0], wj.v[0]);
+        } else if (nb_up) {  // the tile above's last row
+          take(co, true, tile - tc, 1, sd, bit, wb.v[0], wj.v[0], sb, sj);
+        } else {
+          row_zero(wb.v[0]);
+          row_zero(wj.v[0]);
+        }
+        window_row(wr.q[0][1], wr.e[0][1], wb.v[1]);
+        window_row(wr.q[1][1], wr.e[1][1], wj.v[1]);
+        if (in2) {
+          window_row(wr.q[0][2], wr.e[0][2], wb.v[2]);
+          window_row(wr.q[1][2], wr.e[1][2], wj.v[2]);
+        } else if (nb_dn) {  // the tile below's first row
+          take(co, true, tile + tc, 0, sd && !nb_up, bit, wb.v[2], wj.v[2], sb, sj);
+        } else {
+          row_zero(wb.v[2]);
+          row_zero(wj.v[2]);
+        }
+      } else
+#endif
+      {
+        if (ty > 0) {
+          row_lds(sbuf(0, ci) + (ty - 1) * xs, x0, wb.v[0]);
+          row_lds(sbuf(1, ci) + (ty - 1) * xs, x0, wj.v[0]);
+        } else if (nb_up) {  // the tile above's last row (and the side cells)
+          take(co, true, tile - tc, 1, sd, bit, wb.v[0], wj.v[0], sb, sj);
+        } else {
+          row_zero(wb.v[0]);
+          row_zero(wj.v[0]);
+        }
+        row_lds(sbuf(0, ci) + ty * xs, x0, wb.v[1]);
+        row_lds(sbuf(1, ci) + ty * xs, x0, wj.v[1]);
+        if (ty + 1 < a.rt && y + 1 < rows) {
+          row_lds(sbuf(0, ci) + (ty + 1) * xs, x0, wb.v[2]);
+          row_lds(sbuf(1, ci) + (ty + 1) * xs, x0, wj.v[2]);
+        } else if (nb_dn) {  // the tile below's first row (and the side cells)
+          take(co, true, tile + tc, 0, sd && !nb_up, bit, wb.v[2], wj.v[2], sb, sj);
+        } else {
+          row_zero(wb.v[2]);
+          row_zero(wj.v[2]);
+        }
       }
       if (sd && !nb_up && !nb_dn) take(co, false, tile, 0, true, bit, wb.v[1], wj.v[1], sb, sj);
       if (sd_lane) {  // the side neighbour's cells x = -1 (lane 0) / tw (lane 63)
@@ -1468,6 +1584,38 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
     if (valid) {
       if (nb_up || nb_dn) __builtin_amdgcn_s_setprio(2);
       Win6 w;
+#if PP2_RES_SWEEP_WINDOW1 != 0
+      // k_loop_resident's step top: the records of action 0 and every LDS
+      // read of the window rows in one issue burst, before a neighbour's poll.
+      // (One body per ARG: with begin and rest under two branches of their
+      // own the record buffers of both forms stay live between them, and the
+      // kernel spills.)
+      auto sweep_quad = [&](auto with_arg) {
+        constexpr bool ARG = decltype(with_arg)::value;
+        float rtv[2][4][4], rcost[2][4];
+        coded_sweep_iw_pipe_begin<4, ARG>(sTC, iwr, rtv, rcost, best, arg);
+        const bool in0 = ty > 0, in2 = ty + 1 < a.rt && y + 1 < rows;
+        WinRows<1> wr;
+        const float* const wp1[1] = {sbuf(ci) + ty * xs + x0};
+        issue_window_rows<PP2_RES_SWEEP_WINDOW1>(wp1, xs, in0, in2, wr);
+        __builtin_amdgcn_sched_barrier(0);
+        if (in0) window_row(wr.q[0][0], wr.e[0][0], w.v[0]);
+        else if (nb_up) take(co, tile - 1, 1, use[co] & 1u, w.v[0]);
+        else row_zero(w.v[0]);
+        window_row(wr.q[0][1], wr.e[0][1], w.v[1]);
+        if (in2) window_row(wr.q[0][2], wr.e[0][2], w.v[2]);
+        else if (nb_dn) take(co, tile + 1, 0, use[co] & 1u, w.v[2]);
+        else row_zero(w.v[2]);
+        float jn[9][4];
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) jn[i][k] = w.v[i / 3][k + i % 3];
+        coded_sweep_iw_pipe_rest<4, ARG>(sTC, iwr, jn, rtv, rcost, best, arg);
+      };
+      if (check || fin) sweep_quad(std::true_type{});
+      else sweep_quad(std::false_type{});
+#else
       if (ty > 0) row_lds(sbuf(ci) + (ty - 1) * xs, x0, w.v[0]);
       else if (nb_up) take(co, tile - 1, 1, use[co] & 1u, w.v[0]);
       else row_zero(w.v[0]);
@@ -1482,6 +1630,7 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
         for (int k = 0; k < 4; ++k) jn[i][k] = w.v[i / 3][k + i % 3];
       if (check || fin) coded_sweep_iw_pipe<4, true>(sTC, iwr, jn, best, arg);
       else coded_sweep_iw_pipe<4, false>(sTC, iwr, jn, best, arg);
+#endif
       *reinterpret_cast<f4a*>(sbuf(co) + ty * xs + x0) = f4a{best[0], best[1], best[2], best[3]};
       if (nb_up || nb_dn) {
         publish(ci, best, (use[ci] + 1u) & 1u);
