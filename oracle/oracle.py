@@ -2,8 +2,14 @@
 
 TEST INFRASTRUCTURE ONLY.  Only ``tests/``, ``__graft_entry__.smoke()`` and
 ``bench.py``'s ``cpu_baseline`` leg may import this module; the product
-package ``path_planning_2d_amd`` never does.  Parity is unpinned by reference
-tests (the reference ships none) -- see ``pp2_oracle.h`` for the citations each
+package ``path_planning_2d_amd`` never does.  The reference ships no tests; the
+device-kernel restatements (``model_pomdp``, ``model_mdp``, ``mdp_sweep``,
+``belief_update``, ``fib_sweep``, ``pbvi_gamma_ao``) are pinned bit for bit to
+the reference's own kernels built for the host with contracted fma
+(``ref_build.py``, ``ref.py``, ``tests/test_ref_pin_cpu.py``); the host-side
+restatements (normalisation, sampling, the PBVI driver, the QV-tree) and
+cuRAND forward sampling stay unpinned, because that code needs Boost, ROS,
+cuBLAS or cuRAND to build.  See ``pp2_oracle.h`` for the citations each
 function follows.
 
 All arrays use the reference layouts: ``T[hw, 9, 9]``, ``L[hw, 16]``,
@@ -76,6 +82,7 @@ def lib():
             "orc_pbvi_belief_set": (I, [I, I, _f32p, _f32p, _f32p, I, C.c_void_p, _f32p]),
             "orc_pbvi_backup": (I, [I, I, F, _f32p, _f32p, _f32p, I, _f32p, _f32p, _u8p, I]),
             "orc_pbvi_iterations": (I, [F]),
+            "orc_pbvi_gamma_ao": (None, [I, I, F, _f32p, _f32p, I, I, I, _f32p, _f32p]),
             "orc_pbvi_eval": (None, [S, _f32p, I, _f32p, _u8p, C.POINTER(F),
                                      C.POINTER(C.c_uint8)]),
             "orc_heap_sort_desc": (None, [S, _f32p, np.ctypeslib.ndpointer(np.uintp,
@@ -405,6 +412,15 @@ def pbvi_backup(H, W, gamma, T, L, R, b_set, alphas=None, iterations=0):
     if n < 0:
         raise MemoryError("orc_pbvi_backup")
     return al, act, n
+
+
+def pbvi_gamma_ao(H, W, gamma, T, L, a, o, alphas):
+    """cudaComputeGammaOA for one (a, o): out[k, x] for alphas[k, x]."""
+    alphas = np.ascontiguousarray(alphas, np.float32).reshape(-1, H * W)
+    out = np.empty_like(alphas)
+    lib().orc_pbvi_gamma_ao(H, W, float(gamma), T, L, int(a), int(o), alphas.shape[0], alphas,
+                            out)
+    return out
 
 
 def pbvi_iterations(gamma):

@@ -1,7 +1,7 @@
 /*
  * pp2_oracle.c -- CPU restatement of path_planning_2d's hot path.
- * TEST INFRASTRUCTURE ONLY; parity unpinned by reference tests (none exist).
- * See pp2_oracle.h for the contract and the citation root.
+ * TEST INFRASTRUCTURE ONLY.  See pp2_oracle.h for the contract, the citation
+ * root and which functions are pinned to the reference's own kernels.
  *
  * Compile with -ffp-contract=off: every fused multiply-add below is an
  * explicit fmaf() standing for an nvcc contraction in the reference device

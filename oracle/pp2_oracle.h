@@ -6,14 +6,31 @@
  * and bench.py's cpu_baseline leg use it, as the checker / the timed CPU
  * baseline.
  *
- * Parity status: UNPINNED by the reference's own tests -- the reference
- * ships no tests, fixtures or golden vectors, and it cannot be
- * built here (nvcc, ROS, OpenCV, Boost, Eigen are absent).
- * The restatement follows the reference line by line (citations below, all
- * relative to /root/reference/path_planning_2d/), is cross-checked against an
- * independent numpy restatement of the simulator's scatter-form CPU filter
- * (dummy_simulator/src/dummy_simulator.cpp:440-773), and is frozen into
- * tests/golden/ fixtures.
+ * Parity status.  The reference ships no tests, fixtures or golden vectors
+ *  and its host code cannot be built here (nvcc, ROS, OpenCV,
+ * Boost, Eigen are absent), but its per-cell kernels are
+ * plain C++ and are built for the host from the reference's own text
+ * (ref_build.py, ref_shim.h, ref_driver.cpp; output in oracle/_ref/, never
+ * committed).
+ *   PINNED, bit for bit, to that build with g++ -O2 -ffp-contract=fast -mfma
+ *   -fno-fast-math (a*b+c contracted as nvcc --use_fast_math does; x86 FTZ and
+ *   DAZ during the call where denormals are in play), by
+ *   tests/test_ref_pin_cpu.py: orc_model_pomdp, orc_model_mdp (all of
+ *   cudaGenerateModelData and its helpers), orc_mdp_sweep
+ *   (cudaOneStepValueIteration), orc_belief_update (cudaBayesBeliefUpdate),
+ *   orc_fib_sweep (cudaFIBValueIteration) and orc_pbvi_gamma_ao
+ *   (cudaComputeGammaOA).  The same kernels built with -ffp-contract=off
+ *   differ from the oracle by a few ulp, so the fmaf placement below is what
+ *   the pin tests.
+ *   UNPINNED: everything the reference runs on the host or through a CUDA
+ *   library -- normalisation, sampling, the PBVI driver (cuBLAS Sgemm / Sgeam)
+ *   and the QV-tree sit in translation units that need Boost and ROS, and
+ *   cudaForwardSampling needs cuRAND's device API.  Those restatements follow
+ *   the reference line by line (citations below, all relative to the
+ *   reference's path_planning_2d/), are cross-checked against an independent
+ *   numpy restatement of the simulator's scatter-form CPU filter
+ *   (dummy_simulator/src/dummy_simulator.cpp:440-773), and are frozen into
+ *   tests/golden/ fixtures.
  *
  * Layouts are the reference's: T[hw][9 u][9 s'], L[hw][16 z], R/C[hw][9 u],
  * cell idx = y*W + x.
@@ -161,6 +178,10 @@ int orc_pbvi_belief_set(int H, int W, const float* T, const float* L, const floa
 int orc_pbvi_backup(int H, int W, float gamma, const float* T, const float* L, const float* R,
                     int S, const float* b_set, float* alphas, uint8_t* actions, int iterations);
 int orc_pbvi_iterations(float gamma);
+/* cudaComputeGammaOA (:295-343) for one (a, o): out[k][x] for every alpha
+ * k of alphas[S][hw]; device arithmetic (contracted fma, denormals flushed). */
+void orc_pbvi_gamma_ao(int H, int W, float gamma, const float* T, const float* L, int a, int o,
+                       int S, const float* alphas, float* out);
 /* indices sorted as the reference's partial_sort (:264-269) leaves them */
 void orc_heap_sort_desc(size_t n, const float* key, size_t* idx);
 

@@ -164,8 +164,8 @@ int orc_pbvi_iterations(float gamma) {
 }
 
 /* cudaComputeGammaOA (:297-341) for one (a, o): out[k][x] for every alpha k */
-static void gamma_ao(int H, int W, float gamma, const float* T, const float* L, int a, int o,
-                     int S, const float* alphas, float* out) {
+void orc_pbvi_gamma_ao(int H, int W, float gamma, const float* T, const float* L, int a, int o,
+                       int S, const float* alphas, float* out) {
   const size_t n = (size_t)H * W;
   for (int y = 0; y < H; ++y)
     for (int x = 0; x < W; ++x) {
@@ -205,7 +205,7 @@ int orc_pbvi_backup(int H, int W, float gamma, const float* T, const float* L, c
       for (int i = 0; i < S; ++i) /* Gamma_a[a][i] = R[:, a] (:459-467) */
         for (size_t x = 0; x < n; ++x) gaa[(size_t)i * n + x] = R[9 * x + a];
       for (int o = 0; o < 16; ++o) {
-        gamma_ao(H, W, gamma, T, L, a, o, S, alphas, gao);
+        orc_pbvi_gamma_ao(H, W, gamma, T, L, a, o, S, alphas, gao);
         /* Sgemm (:505-513) + max_element per belief (:531-537) */
         for (int i = 0; i < S; ++i) {
           const float* bi = b_set + (size_t)i * n;

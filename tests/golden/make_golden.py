@@ -15,10 +15,13 @@ What is frozen, and where it comes from:
   captured through ctypes: pins the oracle's rand() restatement.
 * ``model_<map>.npz``, ``belief_<map>.npz``, ``mdp_<map>.npz``,
   ``fib_<map>.npz``, ``pbvi_<map>.npz`` -- outputs of the CPU oracle (oracle/pp2_oracle.c), the
-  restatement of the reference kernels.  The reference itself cannot be built
-  or run here, so these are "parity unpinned" vectors that
-  freeze the oracle and feed the GPU tests (which may not read
-  /root/reference).
+  restatement of the reference kernels.  The reference's host code cannot be
+  built or run here; these vectors freeze the oracle and
+  feed the GPU tests (which may not read /root/reference).  The ``model_*``
+  tensors, ``J7`` / ``A7`` of ``mdp_*`` and the 3-sweep FIB state are
+  recomputed from the reference's own kernels built for the host in
+  tests/test_ref_pin_cpu.py; what the reference's host code produces (belief
+  trajectories' normalisation, the solved drivers, PBVI) stays unpinned.
 """
 from __future__ import annotations
 

@@ -1,8 +1,9 @@
 """CPU: the oracle (test infrastructure) against the golden fixtures and
-against independent restatements.  Parity of the oracle with the reference is
-unpinned by reference tests (there are none); these tests pin it as far as the
-reference's own data allows -- real glibc rand() output, the simulator's
-independent scatter-form filter, and numpy restatements of the kernels."""
+against independent restatements.  The reference ships no tests; these tests
+pin the oracle as far as the reference's own data allows -- real glibc rand()
+output, the simulator's independent scatter-form filter, and numpy
+restatements of the kernels.  test_ref_pin_cpu.py pins the device-kernel
+restatements to the reference's own kernels built for the host."""
 import ctypes
 
 import numpy as np
