@@ -83,6 +83,7 @@ def lib():
             "orc_pbvi_backup": (I, [I, I, F, _f32p, _f32p, _f32p, I, _f32p, _f32p, _u8p, I]),
             "orc_pbvi_iterations": (I, [F]),
             "orc_pbvi_gamma_ao": (None, [I, I, F, _f32p, _f32p, I, I, I, _f32p, _f32p]),
+            "orc_fma_chain_nt": (None, [I, I, S, _f32p, _f32p, _f32p]),
             "orc_pbvi_eval": (None, [S, _f32p, I, _f32p, _u8p, C.POINTER(F),
                                      C.POINTER(C.c_uint8)]),
             "orc_heap_sort_desc": (None, [S, _f32p, np.ctypeslib.ndpointer(np.uintp,
@@ -420,6 +421,17 @@ def pbvi_gamma_ao(H, W, gamma, T, L, a, o, alphas):
     out = np.empty_like(alphas)
     lib().orc_pbvi_gamma_ao(H, W, float(gamma), T, L, int(a), int(o), alphas.shape[0], alphas,
                             out)
+    return out
+
+
+def fma_chain_nt(A, B):
+    """The pinned Sgemm chain: C[i, k] = fmaf(A[i, x], B[k, x], acc) over x
+    ascending from +0, denormals kept (A[M, n], B[N, n] -> C[M, N])."""
+    A = np.ascontiguousarray(A, np.float32)
+    B = np.ascontiguousarray(B, np.float32)
+    assert A.ndim == 2 and B.ndim == 2 and A.shape[1] == B.shape[1]
+    out = np.empty((A.shape[0], B.shape[0]), np.float32)
+    lib().orc_fma_chain_nt(A.shape[0], B.shape[0], A.shape[1], A, B, out)
     return out
 
 

@@ -182,6 +182,9 @@ int orc_pbvi_iterations(float gamma);
  * k of alphas[S][hw]; device arithmetic (contracted fma, denormals flushed). */
 void orc_pbvi_gamma_ao(int H, int W, float gamma, const float* T, const float* L, int a, int o,
                        int S, const float* alphas, float* out);
+/* The Sgemm chain as pinned in pp2_oracle_pbvi.c: C[i][k] = fmaf(A[i][x],
+ * B[k][x], acc) over x ascending from +0, no flush; A[M][n], B[N][n], C[M][N]. */
+void orc_fma_chain_nt(int M, int N, size_t n, const float* A, const float* B, float* C);
 /* indices sorted as the reference's partial_sort (:264-269) leaves them */
 void orc_heap_sort_desc(size_t n, const float* key, size_t* idx);
 

@@ -191,14 +191,46 @@ void orc_pbvi_gamma_ao(int H, int W, float gamma, const float* T, const float* L
     }
 }
 
+/* The pinned Sgemm chain (see the head of this file), C[i][k] =
+ * fmaf(A[i][x], B[k][x], acc) over x ascending from acc = +0, nothing flushed:
+ * A[M][n], B[N][n], C[M][N].  Eight k chains are walked side by side
+ * (independent chains, each still in x order: the same bits). */
+void orc_fma_chain_nt(int M, int N, size_t n, const float* A, const float* B, float* C) {
+  for (int i = 0; i < M; ++i) {
+    const float* a = A + (size_t)i * n;
+    float* c = C + (size_t)i * N;
+    int k = 0;
+    for (; k + 8 <= N; k += 8) {
+      const float* b = B + (size_t)k * n;
+      float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      for (size_t x = 0; x < n; ++x)
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(a[x], b[(size_t)j * n + x], acc[j]);
+      for (int j = 0; j < 8; ++j) c[k + j] = acc[j];
+    }
+    for (; k < N; ++k) {
+      const float* b = B + (size_t)k * n;
+      float acc = 0.0f;
+      for (size_t x = 0; x < n; ++x) acc = fmaf(a[x], b[x], acc);
+      c[k] = acc;
+    }
+  }
+}
+
 int orc_pbvi_backup(int H, int W, float gamma, const float* T, const float* L, const float* R,
                     int S, const float* b_set, float* alphas, uint8_t* actions, int iterations) {
   const size_t n = (size_t)H * W;
   if (iterations <= 0) iterations = orc_pbvi_iterations(gamma);
   float* gao = (float*)malloc((size_t)S * n * sizeof(float));
   float* ga = (float*)malloc((size_t)9 * S * n * sizeof(float));
+  float* cm = (float*)malloc((size_t)S * S * sizeof(float));
   int* kstar = (int*)malloc((size_t)S * sizeof(int));
-  if (!gao || !ga || !kstar) return -1;
+  if (!gao || !ga || !cm || !kstar) {
+    free(gao);
+    free(ga);
+    free(cm);
+    free(kstar);
+    return -1;
+  }
   for (int it = 0; it < iterations; ++it) {
     for (int a = 0; a < 9; ++a) {
       float* gaa = ga + (size_t)a * S * n;
@@ -207,16 +239,12 @@ int orc_pbvi_backup(int H, int W, float gamma, const float* T, const float* L, c
       for (int o = 0; o < 16; ++o) {
         orc_pbvi_gamma_ao(H, W, gamma, T, L, a, o, S, alphas, gao);
         /* Sgemm (:505-513) + max_element per belief (:531-537) */
+        orc_fma_chain_nt(S, S, n, b_set, gao, cm);
         for (int i = 0; i < S; ++i) {
-          const float* bi = b_set + (size_t)i * n;
+          const float* ci = cm + (size_t)i * S;
           int best = 0;
-          float bv = 0.0f;
-          for (int k = 0; k < S; ++k) {
-            const float* g = gao + (size_t)k * n;
-            float acc = 0.0f;
-            for (size_t x = 0; x < n; ++x) acc = fmaf(g[x], bi[x], acc);
-            if (k == 0 || bv < acc) { bv = acc; best = k; }
-          }
+          for (int k = 1; k < S; ++k)
+            if (ci[best] < ci[k]) best = k;
           kstar[i] = best;
         }
         /* Sgeam: Gamma_a += alphas_ao_max (:542-550) */
@@ -244,6 +272,7 @@ int orc_pbvi_backup(int H, int W, float gamma, const float* T, const float* L, c
   }
   free(gao);
   free(ga);
+  free(cm);
   free(kstar);
   return iterations;
 }

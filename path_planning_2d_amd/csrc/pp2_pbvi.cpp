@@ -34,7 +34,12 @@ namespace pp2rt {
 
 struct PbviState {
   int S = 0, Sp = 0, ld = 0, hw = 0;
-  float* bset = nullptr;      // [Sp][ld] belief set
+  // [Sp][ld] belief set.  Its pad cells [hw, ld) hold -0, not +0: the GEMM
+  // runs every chain over all ld cells, and a pad term (-0) * (+0) = -0 is
+  // the one addend that leaves every sum as it is, a -0 included, so the
+  // chain ends at hw as the reference's does (a +0 term would turn a chain
+  // that ends at -0 into +0).
+  float* bset = nullptr;
   float* alpha[2] = {nullptr, nullptr};  // [Sp][ld] alpha vectors (ping-pong)
   int acur = 0;
   uint8_t* actions = nullptr;  // [Sp]
@@ -45,6 +50,8 @@ struct PbviState {
   float* Cm = nullptr;   // [group*16][Sp][Sp]  <b_i, Gamma_ao_k>
   int* kstar = nullptr;  // [group*16][Sp]
   float* V = nullptr;    // [9][Sp]
+  int group_alloc = 0;   // the group G, Cm and kstar are sized for
+  int last_group = 0;    // the last backup's group (0: no backup of this state yet)
 };
 
 namespace {
@@ -83,6 +90,7 @@ void free_scratch(PbviState* p) {
   dfree(&p->Cm);
   dfree(&p->kstar);
   dfree(&p->V);
+  p->group_alloc = 0;
 }
 
 // (Re)size the state for S beliefs; alphas and actions are zeroed.
@@ -107,7 +115,10 @@ int ensure_state(pp2_ctx* c, int S) {
   p->ld = ld;
   p->hw = hw;
   const size_t rows = (size_t)Sp * ld;
+  const bool new_bset = !p->bset;
   CHECK(dalloc(&p->bset, rows, c->stream));
+  if (new_bset)  // -0 everywhere; the cells below hw are written before they are read
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)p->bset, (int)0x80000000u, rows, c->stream));
   CHECK(dalloc(&p->alpha[0], rows, c->stream));
   CHECK(dalloc(&p->alpha[1], rows, c->stream));
   CHECK(dalloc(&p->actions, (size_t)Sp, c->stream));
@@ -115,11 +126,12 @@ int ensure_state(pp2_ctx* c, int S) {
   HIPCHK(hipMemsetAsync(p->alpha[1], 0, rows * sizeof(float), c->stream));
   HIPCHK(hipMemsetAsync(p->actions, 0, (size_t)Sp, c->stream));
   p->acur = 0;
+  p->last_group = 0;
   ++c->pbvi_version;
   return PP2_OK;
 }
 
-// dst rows of ld floats <- host rows of hw floats (pad cells stay 0)
+// dst rows of ld floats <- host rows of hw floats (pad cells stay as they are)
 int upload_rows(pp2_ctx* c, float* dst, int ld, const float* src, int hw, int rows) {
   HIPCHK(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), src, (size_t)hw * sizeof(float),
                           (size_t)hw * sizeof(float), rows, hipMemcpyHostToDevice, c->stream));
@@ -228,8 +240,8 @@ int belief_set_impl(pp2_ctx* c, const float* b0, int S, uint32_t seed, uint64_t*
     for (int k = 0; k < take && set_size < S; ++k) {
       const size_t i = order[k];
       HIPCHK(hipMemcpyAsync(p->bset + (size_t)set_size * ld,
-                            w.cand + (size_t)(9 * i + best_a[i]) * ld, (size_t)ld * sizeof(float),
-                            hipMemcpyDeviceToDevice, c->stream));
+                            w.cand + (size_t)(9 * i + best_a[i]) * ld, (size_t)hw * sizeof(float),
+                            hipMemcpyDeviceToDevice, c->stream));  // (the set's pad cells stay -0)
       ++set_size;
     }
     HIPCHK(pp2::launch_rows_seq(c->stream, pp2::ROW_CDF, p->bset + (size_t)first_new * ld, ld,
@@ -245,6 +257,7 @@ int belief_set_impl(pp2_ctx* c, const float* b0, int S, uint32_t seed, uint64_t*
 // Actions whose Gamma_ao slices are resident at once: all 9 (one GEMM
 // launch of 144 batches) when they fit kGaoBudget bytes, else fewer.
 constexpr size_t kGaoBudget = size_t(48) << 30;
+int g_debug_group = 0;  // pp2_debug_pbvi_group: actions per group, 0 = from the budget
 
 int backup_impl(pp2_ctx* c, int iterations) {
   PbviState* p = c->pbvi;
@@ -254,7 +267,14 @@ int backup_impl(pp2_ctx* c, int iterations) {
   const int S = p->S, Sp = p->Sp, ld = p->ld, hw = p->hw;
   const long long gstride = (long long)Sp * ld;
   const size_t per_action = (size_t)16 * gstride * sizeof(float);
-  const int group = (int)std::max<size_t>(1, std::min<size_t>(9, kGaoBudget / per_action));
+  int group = (int)std::max<size_t>(1, std::min<size_t>(9, kGaoBudget / per_action));
+  if (g_debug_group > 0) group = std::min(9, g_debug_group);
+  if (p->group_alloc != group) {  // only pp2_debug_pbvi_group changes it on a kept state
+    dfree(&p->G);
+    dfree(&p->Cm);
+    dfree(&p->kstar);
+    p->group_alloc = group;
+  }
   CHECK(dalloc(&p->G, (size_t)16 * group * gstride, c->stream));
   CHECK(dalloc(&p->Ga, (size_t)9 * gstride, c->stream));
   CHECK(dalloc(&p->Cm, (size_t)16 * group * Sp * Sp, c->stream));
@@ -277,6 +297,7 @@ int backup_impl(pp2_ctx* c, int iterations) {
                                    p->actions));
     p->acur ^= 1;
     ++c->pbvi_version;
+    p->last_group = group;
   }
   return PP2_OK;
 }
@@ -472,4 +493,63 @@ int pp2_pbvi_load(pp2_ctx* c, const char* dir, uint32_t set_size) {
   std::vector<uint8_t> act(set_size);
   CHECK(read_actions(join(dir, "pbvi_actions"), act));
   return pp2_pbvi_set(c, set_size, al.data(), act.data());
+}
+
+// Diagnostics (tests/test_gpu_pbvi_stages.py, not part of pp2.h).
+//
+// pp2_debug_pbvi_stage: one intermediate of the last pp2_pbvi_backup
+// iteration, copied to the host with its padding:
+//   which 0  G     slice index = 16 a + o   [Sp][ld] f32
+//         1  Cm    slice index = 16 a + o   [Sp][Sp] f32
+//         2  kstar slice index = 16 a + o   [Sp]     i32
+//         3  Ga    action index = a         [Sp][ld] f32
+//         4  V     index 0                  [9][Sp]  f32
+// dims (optional) = {S, Sp, ld, hw, actions per group}.  PP2_ESTATE when no
+// backup has run on this state, or (G, Cm, kstar) when the backup ran in
+// groups of fewer than 9 actions, so that the slices of the earlier groups
+// are gone.  Read-only.
+extern "C" int pp2_debug_pbvi_stage(pp2_ctx* c, int which, int index, void* out,
+                                    unsigned long long capacity_bytes, int* dims) {
+  CHECK(check_ctx(c));
+  PbviState* p = c->pbvi;
+  if (!p || p->last_group == 0) return set_err(PP2_ESTATE, "no PBVI backup has run");
+  if (dims) {
+    dims[0] = p->S;
+    dims[1] = p->Sp;
+    dims[2] = p->ld;
+    dims[3] = p->hw;
+    dims[4] = p->last_group;
+  }
+  if (!out) return set_err(PP2_EINVAL, "null output");
+  const size_t Sp = (size_t)p->Sp, ld = (size_t)p->ld;
+  if (which < 0 || which > 4) return set_err(PP2_EINVAL, "unknown PBVI stage %d", which);
+  const int count = which <= 2 ? 144 : which == 3 ? 9 : 1;
+  if (index < 0 || index >= count)
+    return set_err(PP2_EINVAL, "PBVI stage %d has no index %d", which, index);
+  if (which <= 2 && p->last_group < 9)
+    return set_err(PP2_ESTATE, "the backup ran in groups of %d actions: slice not resident",
+                   p->last_group);
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (which) {
+    case 0: src = p->G + (size_t)index * Sp * ld; bytes = Sp * ld * sizeof(float); break;
+    case 1: src = p->Cm + (size_t)index * Sp * Sp; bytes = Sp * Sp * sizeof(float); break;
+    case 2: src = p->kstar + (size_t)index * Sp; bytes = Sp * sizeof(int); break;
+    case 3: src = p->Ga + (size_t)index * Sp * ld; bytes = Sp * ld * sizeof(float); break;
+    default: src = p->V; bytes = 9 * Sp * sizeof(float); break;
+  }
+  if (capacity_bytes < bytes)
+    return set_err(PP2_EINVAL, "buffer of %llu B < %zu B", capacity_bytes, bytes);
+  DeviceGuard dg(c->device);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  return PP2_OK;
+}
+
+// pp2_debug_pbvi_group: the backup's actions per group (1..9; 0 = derived
+// from kGaoBudget, the default).  Returns the previous value.
+extern "C" int pp2_debug_pbvi_group(int n) {
+  const int prev = g_debug_group;
+  g_debug_group = n < 0 ? 0 : std::min(n, 9);
+  return prev;
 }

@@ -72,10 +72,15 @@ __global__ __launch_bounds__(kThreads) void k_tree_pred(Geom g, PlaneSet T,
 // One thread = one cell x, kGaoRows alpha vectors and 8 of the 16
 // observations: the 8x9 products T[x][a][s] * L[nbr_s(x)][o] stay in
 // registers across the alpha rows (blockIdx.z = 2 * action + half).
-// Off-grid neighbours enter as 0 * 0 terms, which leave the chain unchanged
-// (it never holds -0), exactly as the reference's skipped terms.  The slices
-// are written once and read back by the GEMM after more than the Infinity
-// Cache has streamed by: non-temporal stores.
+// The reference skips off-grid neighbours.  Here they enter as (-0) * (+0)
+// terms: the product is -0, the one addend that leaves every sum as it is
+// (x + -0 = x, also for x = -0), so the chain equals the reference's bit for
+// bit.  A (+0) * (+0) term would not: the chain holds -0 whenever a negative
+// product underflows and is flushed, and -0 + +0 = +0.  (Skipping the terms
+// with a select per fmaf gives the same bits and measured 1.1 % slower on the
+// backup at 256 x 256, S = 500.)  The slices are written once and read back
+// by the GEMM after more than the Infinity Cache has streamed by:
+// non-temporal stores.
 __global__ __launch_bounds__(kThreads) void k_pbvi_gamma_ao(
     Geom g, float gamma, PlaneSet T, PlaneSet L, const float* __restrict__ alpha, int ld, int S,
     int a0, float* __restrict__ G, long long ostride) {
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_pbvi_gamma_ao(
     for (int o = 0; o < 8; ++o)
       tm[o][s] = ok[s] ? t * L.p[(long long)(ok[s] ? sy : y) * L.rs + (long long)(o0 + o) * L.ps +
                                  (ok[s] ? sx : x)]
-                       : 0.0f;
+                       : -0.0f;
   }
   const int k1 = min(S, (int)(blockIdx.y + 1) * kGaoRows);
   for (int k = blockIdx.y * kGaoRows; k < k1; ++k) {

@@ -88,6 +88,10 @@ hipError_t launch_pbvi_pick(hipStream_t st, const float* l1, int ldo, int n, int
 // C[z][s][i][k] = x-ordered fmaf chain over the split-s range of x of
 // A[i][x] * B[z][k][x] (v_mfma_f32_32x32x2_f32); Mp, Np multiples of
 // kGemmTile, ld of kPbviChunk.  ksplit = 1: the chain over all x from 0.
+// The chain runs over the pad cells too: with A's pad cells -0 and B's +0
+// every pad term is -0, which changes no sum (x + -0 = x, also for x = -0),
+// and the result is the chain over the unpadded cells bit for bit; with +0
+// in both, a chain that ends at -0 comes out as +0.
 hipError_t launch_gemm_nt(hipStream_t st, const float* A, const float* B, float* C, int Mp,
                           int Np, int ld, int batch, long long bstride, long long cstride,
                           int ksplit, long long sstride);

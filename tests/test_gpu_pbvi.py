@@ -12,6 +12,8 @@ restatement of point_based_value_iteration_cuda.cu.
 * evaluatePbviCpu (:678-699): bit-exact.
 At S = 500 on 100x40 (the reference's configuration) the backup is checked by
 properties: valid actions, finite values, below the FIB upper bound.
+The backup's five kernels are compared one by one, at their tile and padding
+edges and from given alphas, in test_gpu_pbvi_stages.py.
 """
 import os
 
