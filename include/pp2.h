@@ -191,6 +191,15 @@ int pp2_set_cells_per_lane(pp2_ctx* ctx, int cpt);
  *                           equal each other to rounding (power-of-two scales
  *                           are exact); values and actions are bit-identical. */
 #define PP2_TUNE_SHARD_LAG 13
+/*  PP2_TUNE_RESIDENT_MASKED 1 (default): whole-row tiles of the tile-resident
+ *                           loop run its masked-support form on a model that
+ *                           is admitted to it (pp2_resident_masked; every
+ *                           generated model whose goal is a free cell): blocked
+ *                           cells are kept as +0 in the tile and the base
+ *                           kernel's weights are constants, instead of a table
+ *                           read per cell and action.  0 = never.  Results are
+ *                           bit-identical either way. */
+#define PP2_TUNE_RESIDENT_MASKED 15
 /*  Diagnostics (tests):
  *  PP2_TUNE_RESIDENT_CUS    plan resident launches for at most this many CUs
  *                           (0: all); a grid whose tiles do not fit falls
@@ -260,6 +269,11 @@ int pp2_resident_tiling(pp2_ctx* ctx, int* tiles, int* rows_per_tile, int* tile_
  * launches (pp2_loop_run) and resident MDP-solve launches (pp2_mdp_solve);
  * either pointer may be NULL.  No reference counterpart. */
 int pp2_resident_launches(pp2_ctx* ctx, int* loop_launches, int* solve_launches);
+/* Whether the current model is admitted to the masked-support form of the
+ * tile-resident loop (re-evaluated whenever the model is set: generate, upload,
+ * load), and how many of the loop launches counted by pp2_resident_launches
+ * ran it (PP2_TUNE_RESIDENT_MASKED); either pointer may be NULL. */
+int pp2_resident_masked(pp2_ctx* ctx, int* admitted, int* launches);
 /* Resident launches re-run on per-step launches after a timeout, and whether
  * the resident kernels are still enabled on the context (either may be NULL). */
 int pp2_resident_status(pp2_ctx* ctx, int* fallbacks, int* enabled);

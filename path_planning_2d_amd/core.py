@@ -108,6 +108,7 @@ class GridContext:
     TUNE_RESIDENT_TILE_COLS = 12
     TUNE_SHARD_LAG = 13
     TUNE_COMM_TIMING = 14
+    TUNE_RESIDENT_MASKED = 15
 
     def set_tuning(self, key: int, value: int):
         call("pp2_set_tuning", self._h, int(key), int(value))
@@ -139,6 +140,14 @@ class GridContext:
         so = C.c_int()
         call("pp2_resident_launches", self._h, C.byref(lo), C.byref(so))
         return lo.value, so.value
+
+    def resident_masked(self):
+        """(the model is admitted to the resident loop's masked-support form,
+        resident loop launches that ran it)."""
+        ad = C.c_int()
+        n = C.c_int()
+        call("pp2_resident_masked", self._h, C.byref(ad), C.byref(n))
+        return bool(ad.value), n.value
 
     def resident_status(self):
         """(resident launches re-run after a timeout, resident kernels enabled)."""

@@ -251,6 +251,86 @@ __device__ __forceinline__ void coded_sweep_iw_pipe(const float* sTC, const uint
   coded_sweep_iw_pipe_rest<N, ARG>(sTC, iw, jn, tv, cost, best, arg);
 }
 
+// The masked-support form of the pipelined backup (the resident loop's masked
+// whole-row instance; models admitted by pp2_masked.h): every off-centre
+// support weight of a free cell is the base kernel's constant -- gwm for the
+// cell action A points to, gws for its other two -- or +0, and +0 exactly
+// where the neighbour is blocked; the caller's J window holds blocked cells as
+// +0, so fmaf(gw, +0, c) == c stands for the dense chain's fmaf(+0, J, c) == c
+// (finite operands, c never -0) and the surviving terms are the same products
+// in the same order.  Per (action, cell) ONE 8-B record {gT centre, C} from GC
+// (the class offsets of the IW records address its 16-B slots), two record
+// buffers of 2 VGPRs per cell.  A blocked own cell's chain is its centre term
+// alone: ov = fmaf(gT centre, own J, C) of action 0 with the cell's own
+// unmasked J (jo; the window's centre is its masked copy), taken by the caller
+// after action 8 -- all nine of its costs are equal, so the value and the
+// strict-< scan's action (0) are the dense ones.
+template <int N, bool ARG, int A>
+__device__ __forceinline__ void sweep_pipe_action_m(const char* gc, const uint32_t (&iw)[N][3],
+                                                    const float (&jn)[9][N], float gwm, float gws,
+                                                    float (&rec)[2][N][2], float (&ov)[N],
+                                                    float (&best)[N], uint32_t (&arg)[N]) {
+  constexpr int cur = A & 1, nxt = cur ^ 1, B = A + 1;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    if constexpr (B < 9) {
+      uint32_t w = B < 4 ? iw[k][0] : B < 8 ? iw[k][1] : iw[k][2];
+      if constexpr (ARG) asm volatile("" : "+v"(w));  // (as sweep_pipe_action)
+      const uint32_t off = __builtin_amdgcn_ubfe(w, 8 * (B % 4), 8);
+      constexpr int tab = B * kFactK * 16;
+      const f2a r = *reinterpret_cast<const f2a*>(gc + tab + off);
+      rec[nxt][k][0] = r[0];
+      rec[nxt][k][1] = r[1];
+    }
+    if constexpr (A >= 0) {
+      if constexpr (A == 0) ov[k] = __builtin_fmaf(rec[cur][k][0], ov[k], rec[cur][k][1]);
+      float c = rec[cur][k][1];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < kSupN[A]) {
+          const int i = kSup[A][j];
+          const float wt = i == 4 ? rec[cur][k][0] : i == A ? gwm : gws;
+          c = __builtin_fmaf(wt, jn[i][k], c);
+        }
+      if constexpr (ARG) {
+        if (c < best[k]) { best[k] = c; arg[k] = (uint32_t)A; }
+      } else {
+        best[k] = __builtin_fminf(best[k], c);
+      }
+    }
+    if constexpr (B < 9) {
+      __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);  // the record offset of (B, k)
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // its DS read
+    }
+    if constexpr (A >= 0)
+      __builtin_amdgcn_sched_group_barrier(0x002, kSupN[A] + (ARG ? 3 : 1) + (A == 0 ? 1 : 0), 0);
+  }
+}
+// _begin: the records of action 0; _rest: the nine actions.  ov: in, the
+// cells' own unmasked J of the previous step; out, the blocked cells' value.
+template <int N, bool ARG>
+__device__ __forceinline__ void masked_sweep_pipe_begin(const float* sGC, const uint32_t (&iw)[N][3],
+                                                        float (&rec)[2][N][2]) {
+  const char* gc = reinterpret_cast<const char*>(sGC);
+  const float jn[9][N] = {};  // (unused by the -1 stage)
+  float ov[N], best[N];
+  uint32_t arg[N];
+  sweep_pipe_action_m<N, ARG, -1>(gc, iw, jn, 0.0f, 0.0f, rec, ov, best, arg);
+}
+template <int N, bool ARG>
+__device__ __forceinline__ void masked_sweep_pipe_rest(const float* sGC, const uint32_t (&iw)[N][3],
+                                                       const float (&jn)[9][N], float gwm,
+                                                       float gws, float (&rec)[2][N][2],
+                                                       float (&ov)[N], float (&best)[N],
+                                                       uint32_t (&arg)[N]) {
+  const char* gc = reinterpret_cast<const char*>(sGC);
+#pragma unroll
+  for (int k = 0; k < N; ++k) { best[k] = FLT_MAX; arg[k] = 0; }
+#define PP2_PA(AA) sweep_pipe_action_m<N, ARG, AA>(gc, iw, jn, gwm, gws, rec, ov, best, arg);
+  PP2_PA(0) PP2_PA(1) PP2_PA(2) PP2_PA(3) PP2_PA(4) PP2_PA(5) PP2_PA(6) PP2_PA(7) PP2_PA(8)
+#undef PP2_PA
+}
+
 // Bellman backup of 4 cells from their codes (k_mdp_sweep's arithmetic).
 // ARG = false: values only (the resident loop's intermediate steps store no
 // actions), best = minnum over the actions -- the same value as the strict-<

@@ -127,6 +127,8 @@ struct pp2_ctx {
   bool dict_t_finite = false;      // every dictionary T entry is finite
   bool dict_tl_nonneg = false;     // every dictionary T and L entry finite and >= +0
   bool dict_rfact = false;         // d_rfact valid: raw T and L by class (<= 16 each)
+  bool dict_masked = false;        // admitted to the masked-support form (pp2_masked.h)
+  pp2::ResidentMasked res_mw{};    // ... its weights
   // the sparse rows' T == 0 skip needs finite, non-negative beliefs (not -0):
   // false after a pp2_belief_set that breaks that, until the next one
   bool belief_sparse_ok = true;
@@ -173,6 +175,8 @@ struct pp2_ctx {
   // then one error word per journalled launch
   unsigned* res_host = nullptr;
   int res_launches = 0, sol_launches = 0;  // pp2_resident_launches
+  int res_masked = 1;              // PP2_TUNE_RESIDENT_MASKED
+  int res_masked_launches = 0;     // pp2_resident_masked
   // Every resident launch is journalled until verified (resident_settle): its
   // inputs stay intact (outputs go to the other ping-pong buffers), and a
   // launch queued behind an unverified one exits at once if an earlier one

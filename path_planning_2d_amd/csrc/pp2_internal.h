@@ -171,6 +171,16 @@ constexpr int kResQR = 0;
 constexpr int kResLT = 9 * kFactK * 4;
 constexpr int kResTab = kResLT + 16 * kResLK;  // floats of the LDS image
 constexpr int kResLX = kResTab;                // byte table after it (global)
+// Masked-support form of the whole-row loop (pp2_masked.h; models admitted by
+// masked_admit only), after the LX bytes in the global image:
+//   FX  [E] bytes (global only): 1 = the entry is blocked
+//   GC  [9][kFactK] x 4 floats: {gT centre, C_a} of the class at .x / .y (one
+//       8-B record in a 16-B slot, addressed by the same 16 * class offsets)
+constexpr int kResFX = kResLX + 400 / 4;  // (kDictMax bytes of LX before it)
+constexpr int kResGC = kResFX + 400 / 4;
+constexpr int kResGCn = 9 * kFactK * 4;
+constexpr int kResAll = kResGC + kResGCn;  // floats of the global image
+static_assert(kDictMax == 400 && kResGC % 4 == 0, "LX / FX hold kDictMax bytes each");
 constexpr int kFactQT = 0;
 constexpr int kFactCT = 9 * kFactK * 4;
 constexpr int kFactIW = 2 * 9 * kFactK * 4;
@@ -323,6 +333,13 @@ struct ResidentHead {
   unsigned slot_use[2];      // uses of exchange slots 0 / 1 by earlier launches
   int stall_tile;            // diagnostic (tests): this tile returns at once, -1 none
 };
+// The masked-support instance's extra kernel argument (pp2_masked.h): the
+// base kernel's two off-centre weights, raw (belief gather) and fl(gamma * w)
+// (backup).  Passed beside the head, so that the other instances' kernel
+// arguments keep their layout.
+struct ResidentMasked {
+  float w_main, w_side, gw_main, gw_side;
+};
 // Runs of at most kResidentShortSteps steps launch a kernel instance whose
 // trajectory argument holds just that many steps: 256 B of kernel arguments
 // instead of ~2.3 KB, about 3 us less host time per launch from an idle
@@ -359,6 +376,8 @@ struct SweepRun {
   int stall_tile;      // diagnostic (tests): this tile returns at once, -1 none
 };
 size_t resident_lds_bytes(const Geom& g, int E, int rt, int tc);
+// The masked-support instance's (whole-row tiles): no class planes.
+size_t resident_masked_lds_bytes(const Geom& g, int E, int rt);
 // Plans fail (the caller falls back BEFORE launching) unless every tile can
 // be resident at once: occupancy per CU x ncus >= tiles (one 1024-lane
 // workgroup per CU at these LDS sizes).
@@ -390,7 +409,12 @@ inline Geom transposed_geom(const Geom& g) {
   t.halo = 0;
   return t;
 }
-hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const ResidentRun& a);
+// masked: run the masked-support instance (an unsharded whole-row plan of a
+// model admitted by masked_admit, the FX / GC tables in a.rfact) when the
+// library was built with it (resident_masked_built), else null.
+hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const ResidentRun& a,
+                                const ResidentMasked* masked = nullptr);
+bool resident_masked_built();
 // Row-shard boundary kernels (pp2_resident.hip).  vec holds one
 // record of kVecRec floats per rank, {owned mass, shift, lost}: the mass of the
 // n partials (k_sum_finalize's tree), (float) *shift (0 if shift is null) and,

@@ -490,6 +490,70 @@ __device__ __forceinline__ void belief_any_pre(int u, int x0, uint32_t lx4, int 
   }
 }
 
+// The masked-support form of the whole-row instance (models
+// admitted by pp2_masked.h; 0 compiles the instance out and every launch runs
+// the class-table form).  The tile's LDS planes and the published granules
+// hold b and J with blocked cells stored as +0 (the lane's own unmasked values
+// persist in p / best), so an off-centre weight is the wave-uniform constant
+// of the base kernel and the zero sits in the operand: no class planes, no QR
+// quads, one 8-B {gT centre, C} record per (action, cell) in the backup.
+#ifndef PP2_RES_MASKED
+#define PP2_RES_MASKED 1
+#endif
+// The gather of action U (belief_fact's support positions and ascending-s
+// order): an off-centre term is fmaf(w, window value, p) with the scalar
+// weight -- wm for the source cell that action U moves onto this one (T index
+// U), ws for the other two -- the centre term takes tc[k], the raw centre T of
+// the cell's own class (QR[U][class][centre slot], read by the caller at the
+// step's top), and a blocked own cell's chain is its centre term alone, on its
+// own unmasked belief bo[k] (its window value is the masked copy).  The dense
+// chain's terms with T == +0 are fmaf(+0, b, p) == p, the masked ones
+// fmaf(w, +0, p) == p (finite w and b, p never -0): the same bits.
+template <int U>
+__device__ __forceinline__ void belief_masked(float wm, float ws, const float (&tc)[4],
+                                              const float (&lz)[4], const float (&mk)[4],
+                                              const float (&bo)[4], const Win6& win,
+                                              float (&p)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k] = 0.0f;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int wr = s / 3, wc = s % 3 - 1, i = 8 - s;
+    if (kSupSlot.s[U][i] < 0) continue;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float wt = i == 4 ? tc[k] : i == U ? wm : ws;
+      p[k] = __builtin_fmaf(wt, win.v[wr][k + 1 + wc], p[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float own = __builtin_fmaf(tc[k], bo[k], 0.0f);
+    p[k] = (mk[k] == 0.0f ? own : p[k]) * lz[k];
+  }
+}
+[[maybe_unused]] __device__ __forceinline__ void belief_any_masked(
+    int u, float wm, float ws, const float (&tc)[4], const float (&lz)[4], const float (&mk)[4],
+    const float (&bo)[4], const Win6& w, float (&p)[4]) {
+  switch (u) {
+#define PP2_BQ(UU)                                        \
+  case UU:                                                \
+    belief_masked<UU>(wm, ws, tc, lz, mk, bo, w, p);      \
+    break;
+    PP2_BQ(0) PP2_BQ(1) PP2_BQ(2) PP2_BQ(3) PP2_BQ(4) PP2_BQ(5) PP2_BQ(6) PP2_BQ(7)
+    default: belief_masked<8>(wm, ws, tc, lz, mk, bo, w, p);
+#undef PP2_BQ
+  }
+}
+// byte offset of action u's centre slot in a QR quad: 4 * sup_slot(u, 4)
+struct CentreSlots {
+  unsigned long long v;
+  constexpr CentreSlots() : v(0) {
+    for (int u = 0; u < 9; ++u) v |= (unsigned long long)(4 * sup_slot(u, 4)) << (4 * u);
+  }
+};
+constexpr CentreSlots kCentreSlot{};
+
 // One window row (x0 - 1 .. x0 + 4) from a zero-padded LDS row: the lane's
 // aligned 16 B, and x0 - 1 / x0 + 4 from the neighbouring lanes' quads by DPP
 // wave shifts (wave_shr:1 / wave_shl:1; a wave holds 64 consecutive quads of
@@ -788,10 +852,21 @@ struct alignas(4) Trajectory {  // (read as words: CAP % 4 == 0)
 // TC = 3: the 2-D tiling (2 tile columns) with at most 768 threads -- 3 waves
 // per SIMD, so a 168-VGPR budget instead of 128: the sweep's table reads of
 // all 4 cells of an action in flight together (coded_sweep_iw G = 4).
-template <int CAP, int TC, bool LAG, bool TR>
+// MW: empty, or one ResidentMasked -- the masked-support form (PP2_RES_MASKED;
+// the whole-row instance only) with its weights as a third kernel argument
+// (the other instances' arguments are the two they were).
+__device__ __forceinline__ ResidentMasked masked_arg() { return ResidentMasked{}; }
+[[maybe_unused]] __device__ __forceinline__ ResidentMasked masked_arg(const ResidentMasked& m) {
+  return m;
+}
+template <int CAP, int TC, bool LAG, bool TR, class... MW>
 __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_resident(
-    const ResidentHead a, const Trajectory<CAP> tr) {
+    const ResidentHead a, const Trajectory<CAP> tr, const MW... mwa) {
   static_assert(!TR || TC == 1, "transposed tiles are whole kernel rows");
+  constexpr bool MSK = sizeof...(MW) != 0;
+  static_assert(!MSK || (TC == 1 && !LAG && !TR), "the masked form is a whole-row instance");
+  const ResidentMasked mw = masked_arg(mwa...);
+  (void)mw;
   constexpr int kSweepG = TC == 3 ? 4 : TC > 1 ? 2 : 0;
   // the whole-row instance: the software-pipelined backup (coded_sweep_iw_pipe)
   constexpr bool kSweepPipe = TC == 1 && !LAG && !TR;
@@ -805,9 +880,12 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // LDS: class tables (QR, LT: constant offsets), factored sweep rows (QT, CT:
   // constant offsets; IW), class planes, b buffers 0, 1, J buffers 0, 1
   const int prows = a.rt + 2, ps = tw + 8;
+  // (MSK: the GC records in the class planes' place)
   float* sTC = lds + lds_span(kResTab);  // (stage_rows writes up to the span)
   uint8_t* sP = reinterpret_cast<uint8_t*>(sTC + lds_span(rows_floats(a.E, true)));
-  float* sB0 = reinterpret_cast<float*>(sP) + lds_span(9 * prows * ps / 4);
+  float* sB0 = reinterpret_cast<float*>(sP) + lds_span(MSK ? kResGCn : 9 * prows * ps / 4);
+  const float* sGC = reinterpret_cast<const float*>(sP);
+  (void)sGC;
   float* sS = sB0 + 4 * bufn;
   float* sRed = sS + 16;  // (red_lds) the lagged block start's partials
 
@@ -957,6 +1035,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   }
   stage_rows(a.rfact, kResTab, lds);
   stage_rows(a.rows, rows_floats(a.E, true), sTC);
+  if constexpr (MSK) stage_rows(a.rfact + kResGC, kResGCn, reinterpret_cast<float*>(sP));
   for (int i = threadIdx.x; i < 4 * (a.rt + 1); i += blockDim.x) {
     const int buf = i / (a.rt + 1), r = i % (a.rt + 1);
     *reinterpret_cast<f4a*>(sB0 + buf * bufn + r * xs) = f4a{0.0f, 0.0f, 0.0f, 0.0f};
@@ -976,6 +1055,16 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
 #pragma unroll
     for (int k = 0; k < 4; ++k) lx4 |= (uint32_t)lx[cc[k]] << (8 * k);
   }
+  // MSK: the cells' store masks, 0 for a blocked cell (FX), else 1 -- a 0 / 1
+  // multiplier is exact on the finite, >= +0 values of b and J
+  float mk[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+  if constexpr (MSK) {
+    if (valid) {
+      const uint8_t* fx = reinterpret_cast<const uint8_t*>(a.rfact + kResFX);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) mk[k] = fx[cc[k]] ? 0.0f : 1.0f;
+    }
+  }
   __syncthreads();  // the staged tables
   PP2_RP(1);
 #pragma unroll
@@ -986,7 +1075,8 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // class planes of rows trow*rt-1 .. trow*rt+rt: byte x+4 of plane a, row r
   // = 16 * class of cell (y, gx + x) for action a (0 off the grid; the pads
   // hold the side neighbours' cells x = -1 / tw, 0 at the grid's x edges)
-  for (int i = threadIdx.x; i < prows * tpr; i += blockDim.x) {
+  // (MSK: no class planes)
+  for (int i = threadIdx.x; !MSK && i < prows * tpr; i += blockDim.x) {
     const int r = i / tpr, xq = (i % tpr) * 4, yy = trow * a.rt + r - 1;
     uint32_t pl[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     if (yy >= 0 && yy < rows) {
@@ -1012,7 +1102,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     for (int q = 0; q < 9; ++q)
       *reinterpret_cast<uint32_t*>(sP + (q * prows + r) * ps + 4 + xq) = pl[q];
   }
-  for (int i = threadIdx.x; i < 9 * prows; i += blockDim.x) {
+  for (int i = threadIdx.x; !MSK && i < 9 * prows; i += blockDim.x) {
     const int q = i / prows, yy = trow * a.rt + i % prows - 1;
     uint32_t lp = 0u, rp = 0u;
     if (yy >= 0 && yy < rows) {
@@ -1036,7 +1126,19 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   if (prior_err != 0u) return;  // (uniform: before any global store)
   const bool bnd = nb_up || nb_dn || sd_l || sd_r;  // waves that cross CUs
   if (valid) {
-    const f4a b = b_t, j = j_t;
+    f4a b = b_t, j = j_t;
+    if constexpr (MSK) {  // blocked cells as +0 in the planes and the granules
+      // (the unmasked quads wait in the lane's own place of buffers 1, free
+      // until step 0's stores, for p / best below: held in registers over the
+      // pending-mass reduction they spill)
+      *reinterpret_cast<f4a*>(sbuf(0, 1) + ty * xs + x0) = b;
+      *reinterpret_cast<f4a*>(sbuf(1, 1) + ty * xs + x0) = j;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        b[k] = b[k] * mk[k];
+        j[k] = j[k] * mk[k];
+      }
+    }
     *reinterpret_cast<f4a*>(sbuf(0, 0) + ty * xs + x0) = b;
     *reinterpret_cast<f4a*>(sbuf(1, 0) + ty * xs + x0) = j;
     if (bnd) {
@@ -1117,6 +1219,17 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   auto lag_target = [&](int T) { return a.arrive_base + (unsigned)(T / a.depth - 1) * a.ntiles; };
   float p[4] = {0.0f, 0.0f, 0.0f, 0.0f}, best[4] = {0.0f, 0.0f, 0.0f, 0.0f}, local = 0.0f;
   uint32_t arg[4] = {0u, 0u, 0u, 0u};
+  if constexpr (MSK) {  // the lane's own unmasked b and J, carried from step to step
+    if (valid) {
+      const f4a b = *reinterpret_cast<const f4a*>(sbuf(0, 1) + ty * xs + x0);
+      const f4a j = *reinterpret_cast<const f4a*>(sbuf(1, 1) + ty * xs + x0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        p[k] = b[k];
+        best[k] = j[k];
+      }
+    }
+  }
   PP2_RP(2);
 
   // The trajectory as aligned words through a uniform index (s_load_dword; a
@@ -1264,11 +1377,37 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       // land in the same LDS round trip: the gather's class dwords and the
       // backup's records of action 0
       ClassRows crow;
-      if constexpr (kSweepPipe) load_class_rows(class_rows_of(u, sP, prows, ps, ty), ps, x0, crow);
+      if constexpr (kSweepPipe && !MSK)
+        load_class_rows(class_rows_of(u, sP, prows, ps, ty), ps, x0, crow);
       float rtv[2][4][4], rcost[2][4];
-      if constexpr (kSweepPipe) {
+      if constexpr (kSweepPipe && !MSK) {
         if (last) coded_sweep_iw_pipe_begin<4, true>(sTC, iwr, rtv, rcost, best, arg);
         else coded_sweep_iw_pipe_begin<4, false>(sTC, iwr, rtv, rcost, best, arg);
+      }
+      // MSK: in the class dwords' place the cells' raw centre T of action u
+      // (QR at the class offsets of the IW records in registers: no dependent
+      // round trip) and their L_z, then the {gT centre, C} records of action 0
+      float tcv[4], lzv[4], mrec[2][4][2];
+      if constexpr (MSK) {
+        const char* qr = reinterpret_cast<const char*>(lds + kResQR) + u * (kFactK * 16) +
+                         (int)((kCentreSlot.v >> (4 * u)) & 15u);
+        const char* lt = reinterpret_cast<const char*>(lds + kResLT) + z * (kResLK * 4);
+        // byte u of the cell's 12 IW bytes by two byte permutes with uniform
+        // selectors (bytes 0-7, then byte 8 over it; 0x0c: a zero byte) -- a
+        // select of the three words by u is turned into an indexed read of
+        // iwr, which moves the array to scratch
+        const uint32_t sel0 = 0x0c0c0c00u | (uint32_t)(u & 7);
+        const uint32_t sel1 = 0x0c0c0c00u | (u == 8 ? 4u : 0u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t lo = __builtin_amdgcn_perm(iwr[k][1], iwr[k][0], sel0);
+          tcv[k] = *reinterpret_cast<const float*>(qr + __builtin_amdgcn_perm(iwr[k][2], lo, sel1));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          lzv[k] = *reinterpret_cast<const float*>(lt + __builtin_amdgcn_ubfe(lx4, 8 * k, 8));
+        if (last) masked_sweep_pipe_begin<4, true>(sGC, iwr, mrec);
+        else masked_sweep_pipe_begin<4, false>(sGC, iwr, mrec);
       }
 #if PP2_RES_WINDOW1 != 0
       if constexpr (kSweepPipe) {
@@ -1347,6 +1486,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         for (int i = 0; i < (kClsSlots + 1) / 2; ++i) asm volatile("" : "+v"(creg.lh[i]));
         belief_any_regs(u, creg, lx4, z, wb, p);
       }
+      else if constexpr (MSK) {
+        const float bo[4] = {p[0], p[1], p[2], p[3]};
+        belief_any_masked(u, mw.w_main, mw.w_side, tcv, lzv, mk, bo, wb, p);
+        if constexpr (PP2_RES_EARLY != 0) {
+          if (early) early_arrive();
+        }
+      }
       else if constexpr (kSweepPipe) {
         belief_any_pre<TR>(u, x0, lx4, z, wb, crow, p);
         if constexpr (PP2_RES_EARLY != 0) {
@@ -1360,7 +1506,23 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
 #pragma unroll
         for (int k = 0; k < 4; ++k) jn[i][k] = TR ? wj.v[i % 3][k + i / 3] : wj.v[i / 3][k + i % 3];
       // (2-D tiles: the cells' table reads in pairs, coded_sweep_iw)
-      if constexpr (kSweepPipe) {  // (actions: last step only)
+      if constexpr (MSK) {
+        // ov: the cells' own unmasked J in, the blocked cells' value out
+        float ov[4] = {best[0], best[1], best[2], best[3]};
+        if (last)
+          masked_sweep_pipe_rest<4, true>(sGC, iwr, jn, mw.gw_main, mw.gw_side, mrec, ov, best, arg);
+        else
+          masked_sweep_pipe_rest<4, false>(sGC, iwr, jn, mw.gw_main, mw.gw_side, mrec, ov, best, arg);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const bool blocked = mk[k] == 0.0f;
+          best[k] = blocked ? ov[k] : best[k];
+          arg[k] = blocked ? 0u : arg[k];
+        }
+        *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) =
+            f4a{best[0] * mk[0], best[1] * mk[1], best[2] * mk[2], best[3] * mk[3]};
+        return;
+      } else if constexpr (kSweepPipe) {  // (actions: last step only)
         if (last) coded_sweep_iw_pipe_rest<4, true>(sTC, iwr, jn, rtv, rcost, best, arg);
         else coded_sweep_iw_pipe_rest<4, false>(sTC, iwr, jn, rtv, rcost, best, arg);
       } else {
@@ -1377,6 +1539,16 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       if (mass && !early) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) local += p[k];
+      }
+      if constexpr (MSK) {
+        const float pm[4] = {p[0] * mk[0], p[1] * mk[1], p[2] * mk[2], p[3] * mk[3]};
+        *reinterpret_cast<f4a*>(sbuf(0, co) + ty * xs + x0) = f4a{pm[0], pm[1], pm[2], pm[3]};
+        if (bnd) {
+          const float jm[4] = {best[0] * mk[0], best[1] * mk[1], best[2] * mk[2], best[3] * mk[3]};
+          if (!last) publish(ci, pm, jm, (use[ci] + 1u) & 1u);
+          __builtin_amdgcn_s_setprio(0);
+        }
+        return;
       }
       *reinterpret_cast<f4a*>(sbuf(0, co) + ty * xs + x0) = f4a{p[0], p[1], p[2], p[3]};
       if (bnd) {
@@ -1475,6 +1647,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   if (a.scale_out && tile == 0 && threadIdx.x == 0) *a.scale_out = shift;
   PP2_RP(3);
 }
+
 
 // ---------------------------------------------------------------- MDP solve
 // pp2_mdp_solve's value iteration (valueIteration, src/mdp/path_planning_2d.cu:
@@ -1705,6 +1878,14 @@ size_t resident_lds_bytes(const Geom& g, int E, int rt, int tc) {
          sizeof(float);
 }
 
+size_t resident_masked_lds_bytes(const Geom& g, int E, int rt) {
+  return ((size_t)lds_span(kResTab) + lds_span(rows_floats(E, true)) + lds_span(kResGCn) +
+          4 * (4 + (size_t)rt * (g.wp + 4)) + 16) *
+         sizeof(float);
+}
+
+bool resident_masked_built() { return PP2_RES_MASKED != 0; }
+
 // The plan with tc tile columns: rt rows per tile so that the tiles fit the
 // CUs, or false.
 // The kernel instance of a tiling: 2-D tiles of <= 768 threads run the
@@ -1749,6 +1930,30 @@ static bool resident_plan_tc(const Geom& g, int E, int ncus, int tc, ResidentPla
     }
     nb = std::min(nb, n1);
   }
+#if PP2_RES_MASKED
+  // the masked-support instances of a whole-row plan (less LDS: no class
+  // planes; the tiling is the plan's)
+  if (ktc == 1 && !trn) {
+    static unsigned long long mattr[2] = {};
+    const void* km[2] = {
+        reinterpret_cast<const void*>(
+            &k_loop_resident<kResidentShortSteps, 1, false, false, ResidentMasked>),
+        reinterpret_cast<const void*>(
+            &k_loop_resident<kResidentMaxSteps, 1, false, false, ResidentMasked>)};
+    for (int k = 0; k < 2; ++k) {
+      allow_lds(km[k], mattr[k]);
+      int n1 = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, km[k], (int)threads,
+                                                       resident_masked_lds_bytes(g, E, rt)) !=
+              hipSuccess ||
+          n1 < 1) {
+        (void)hipGetLastError();
+        return false;
+      }
+      nb = std::min(nb, n1);
+    }
+  }
+#endif
   p->rt = rt;
   p->tc = tc;
   p->tr = trn;
@@ -1789,7 +1994,8 @@ bool resident_plan(const Geom& g, int E, int ncus, ResidentPlan* p, int tc_pref,
   return ok1;
 }
 
-hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const ResidentRun& a) {
+hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const ResidentRun& a,
+                                const ResidentMasked* masked) {
   if (a.n < 1 || a.n > kResidentMaxSteps || a.ntiles != p.ntiles || a.rt != p.rt || a.tc != p.tc ||
       a.depth < 1 || a.depth > kResidentRing - 2 || a.own0 < 0 || a.own1 > (p.tr ? a.g.wp : a.g.rows) ||
       a.own0 >= a.own1 || a.b_out == a.b_in || a.j_out == a.j_in ||
@@ -1815,6 +2021,27 @@ hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const Res
                          dim3(p.threads), lds, st, h, tr);                                       \
   } while (0)
   const int ktc = resident_tc(p.tc, p.threads);
+  if (masked) {
+#if PP2_RES_MASKED
+    if (ktc != 1 || p.tr || lag || a.shard || a.red_lds) return hipErrorInvalidValue;
+    const size_t mlds = resident_masked_lds_bytes(a.g, a.E, p.rt);
+    const ResidentMasked mw = *masked;
+    if (a.n <= kResidentShortSteps) {
+      Trajectory<kResidentShortSteps> tr{};
+      std::memcpy(tr.uz, a.uz, (size_t)a.n);
+      hipLaunchKernelGGL((k_loop_resident<kResidentShortSteps, 1, false, false, ResidentMasked>),
+                         dim3(p.ntiles), dim3(p.threads), mlds, st, h, tr, mw);
+    } else {
+      Trajectory<kResidentMaxSteps> tr;
+      std::memcpy(tr.uz, a.uz, sizeof tr.uz);
+      hipLaunchKernelGGL((k_loop_resident<kResidentMaxSteps, 1, false, false, ResidentMasked>),
+                         dim3(p.ntiles), dim3(p.threads), mlds, st, h, tr, mw);
+    }
+    return hipGetLastError();
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
   if (a.n <= kResidentShortSteps) {
     Trajectory<kResidentShortSteps> tr{};
     std::memcpy(tr.uz, a.uz, (size_t)a.n);

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "pp2_ctx.h"
+#include "pp2_masked.h"
 
 using pp2::Geom;
 using pp2::PlaneSet;
@@ -382,6 +383,17 @@ bool coded_active(const pp2_ctx* c) {
   return c->use_coded && c->dict_n > 0 && c->cpt == 4 && (!c->dict_sparse || c->belief_sparse_ok);
 }
 
+// pp2_masked.h restates the base kernels' supports (it includes no HIP header)
+static constexpr bool masked_supports_agree() {
+  for (int a = 0; a < 9; ++a) {
+    if (pp2::masked_detail::kN[a] != pp2::kSupN[a]) return false;
+    for (int j = 0; j < 4; ++j)
+      if (pp2::masked_detail::kS[a][j] != pp2::kSup[a][j]) return false;
+  }
+  return true;
+}
+static_assert(masked_supports_agree(), "pp2_masked.h: kSup / kSupN");
+
 // +0 <= v < +inf (sign bit clear, not inf or NaN)
 static bool finite_nonneg(float v) {
   uint32_t bits;
@@ -403,6 +415,7 @@ int build_model_dict(pp2_ctx* c) { return build_model_dict(c, &c->T, &c->L, &c->
 int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Planes* mR,
                      const Planes* mC) {
   c->dict_n = 0;
+  c->dict_masked = false;
   c->res_e_dict = -1;  // shard_resident_e: recomputed (collectively) on the next run
   ++c->agree_gen;      // ... and agreed again (pp2_loop_run)
   const long long n = (long long)(c->g.rows + 2 * c->g.halo) * c->g.wp;
@@ -413,7 +426,7 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
         hipMalloc(&c->d_rows, ((size_t)pp2::kDictMax * pp2::kDictTC + 4) * sizeof(float)) != hipSuccess ||
         hipMalloc(&c->d_dl, (size_t)pp2::kDictMax * 16 * sizeof(float)) != hipSuccess ||
         hipMalloc(&c->d_tu, ((size_t)9 * pp2::kDictMax * 9 + 4) * sizeof(float)) != hipSuccess ||
-        hipMalloc(&c->d_rfact, ((size_t)pp2::kResTab + pp2::kDictMax / 4 + 4) * sizeof(float)) !=
+        hipMalloc(&c->d_rfact, ((size_t)pp2::kResAll + 4) * sizeof(float)) !=
             hipSuccess)
       return set_err(PP2_ENOMEM, "hipMalloc model dictionary");
     HIPCHK(hipMemsetAsync(c->code_alloc, 0, (size_t)(n + 2 * kGuard) * sizeof(uint16_t), c->stream));
@@ -524,7 +537,7 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
   // determine T in general).
   std::vector<uint32_t> fact_iw((size_t)E * 4, 0u);
   std::vector<float> fact_qt(9 * pp2::kFactK * 4, 0.0f), fact_ct(9 * pp2::kFactK * 4, 0.0f);
-  std::vector<float> rfact((size_t)pp2::kResTab + pp2::kDictMax / 4 + 4, 0.0f);
+  std::vector<float> rfact((size_t)pp2::kResAll + 4, 0.0f);
   for (int a = 0; a < 9 && sparse; ++a) {
     std::vector<std::array<uint32_t, 9>> pairs;
     for (int e = 0; e < E && sparse; ++e) {
@@ -565,6 +578,37 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
           std::memcpy(&rfact[pp2::kResLT + z * pp2::kResLK + k], &key[z], 4);
       }
       lx[e] = (uint8_t)(4 * k);
+    }
+  }
+  // Masked-support form of the whole-row resident loop (pp2_masked.h): the
+  // unsharded grid's rows [-1, rows] against the admission rule; on admission
+  // the blocked-entry bytes FX, the {gT centre, C} records GC of the classes
+  // and the base kernel's two weights (gamma * w rounded once, as fact_qt).
+  bool masked = false;
+  pp2::ResidentMasked mw{};
+  if (rfact_ok && tl_nonneg && t_finite && c->g.halo >= 1 && c->g.row0 == 0 &&
+      c->g.grows == c->g.rows) {
+    const pp2::MaskedModel mm =
+        pp2::masked_admit(code.data() + (size_t)(c->g.halo - 1) * c->g.wp, c->g.wp, c->g.rows,
+                          dh.data(), E, pp2::kDictRow, gam);
+    if (mm.ok) {
+      uint8_t* fx = reinterpret_cast<uint8_t*>(&rfact[pp2::kResFX]);
+      for (int e = 0; e < E; ++e) fx[e] = mm.blocked[e];
+      for (int a = 0; a < 9; ++a) {
+        int cs = 0;
+        for (int j = 0; j < pp2::kSupN[a]; ++j)
+          if (pp2::kSup[a][j] == 4) cs = j;
+        for (int k = 0; k < pp2::kFactK; ++k) {
+          float* rec = &rfact[pp2::kResGC + (a * pp2::kFactK + k) * 4];
+          rec[0] = fact_qt[(a * pp2::kFactK + k) * 4 + cs];
+          rec[1] = fact_ct[(a * pp2::kFactK + k) * 4];
+        }
+      }
+      mw.w_main = mm.w_main;
+      mw.w_side = mm.w_side;
+      mw.gw_main = gam * mm.w_main;
+      mw.gw_side = gam * mm.w_side;
+      masked = true;
     }
   }
   const int tw = pp2::tu_width(sparse);
@@ -609,6 +653,8 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
   c->dict_t_finite = t_finite;
   c->dict_tl_nonneg = tl_nonneg;
   c->dict_rfact = rfact_ok;
+  c->dict_masked = masked;
+  c->res_mw = mw;
   c->dict_n = E;
   return PP2_OK;
 }
@@ -1308,8 +1354,14 @@ static int loop_resident(pp2_ctx* c, int n, const uint8_t* us, const uint8_t* zs
     a.scale_out = nullptr;
     for (int k = 0; k < m; ++k) a.uz[k] = (uint8_t)(us[i + k] | (zs[i + k] << 4));
     a.err_host = journal(c, 1, m, us + i, zs + i);
-    CHECK(gated_launch(c, [&] { return pp2::launch_loop_resident(c->stream, p, a); }));
+    // the masked-support instance: whole-row tiles of an admitted model
+    const bool msk = c->dict_masked && c->res_masked && p.tc == 1 && !p.tr &&
+                     pp2::resident_masked_built();
+    CHECK(gated_launch(c, [&] {
+      return pp2::launch_loop_resident(c->stream, p, a, msk ? &c->res_mw : nullptr);
+    }));
     ++c->res_launches;
+    c->res_masked_launches += msk;
     int arrivals = 0;
     for (int t = 0; t + 1 < m; ++t) arrivals += (c->kstep + t + 1) % depth == 0;
     count_slot_uses(c, 0, m - 1);  // the last step publishes nothing
@@ -1740,6 +1792,10 @@ int pp2_set_tuning(pp2_ctx* c, int key, int value) {
       c->resident = value;
       c->res_e_dict = -1;
       return PP2_OK;
+    case PP2_TUNE_RESIDENT_MASKED:
+      if (value < 0 || value > 1) return set_err(PP2_EINVAL, "resident masked %d not in [0, 1]", value);
+      c->res_masked = value;
+      return PP2_OK;
     case PP2_TUNE_RESIDENT_STALL:
       if (value < -1) return set_err(PP2_EINVAL, "stall tile %d < -1", value);
       c->res_stall_tile = value;
@@ -2099,6 +2155,13 @@ int pp2_resident_launches(pp2_ctx* c, int* loop_launches, int* solve_launches) {
   CHECK(check_ctx_settled(c));
   if (loop_launches) *loop_launches = c->res_launches;
   if (solve_launches) *solve_launches = c->sol_launches;
+  return PP2_OK;
+}
+
+int pp2_resident_masked(pp2_ctx* c, int* admitted, int* launches) {
+  CHECK(check_ctx_settled(c));
+  if (admitted) *admitted = c->dict_n > 0 && c->dict_masked;
+  if (launches) *launches = c->res_masked_launches;
   return PP2_OK;
 }
 
