@@ -500,6 +500,39 @@ __device__ __forceinline__ void belief_any_pre(int u, int x0, uint32_t lx4, int 
 #ifndef PP2_RES_MASKED
 #define PP2_RES_MASKED 1
 #endif
+// The masked instances' step without most of its non-arithmetic VALU work
+// (profiles/r12; 0 compiles them to the earlier instructions;
+// the other instances are the same either way):
+//   * every window row is read from LDS into the same registers, whatever its
+//     source.  The tile buffers are laid out with a row that is never written
+//     in front of each and behind the last (lean_tile_floats), so rows ty - 1
+//     and ty + 1 exist for every wave -- a tile row, or zeros: off the grid, or
+//     a neighbour tile's, whose granules are then OR-ed over the zeros -- and
+//     the six row addresses are one parity offset plus constants.  The earlier
+//     form reads the two rows under wave-uniform branches, so their registers
+//     stay live, undefined, on the paths that take the row from elsewhere and
+//     the merge costs a v_mov per value (26 per interior wave-step, 12 zero
+//     moves more per off-grid or neighbour row).  (A single row of zeros
+//     behind the buffers, with each row's offset chosen by scalar selects ahead
+//     of the reads, removes the same copies but gives most of the gain back:
+//     profiles/r12.);
+//   * the masked J quad (best * mk) is written once, for the LDS store and the
+//     publish, and the blocked cells' action select of a step that stores no
+//     actions is skipped;
+//   * the masked launch is never a shard's (no shard scale), and the publish
+//     tests its four role flags as bits of one SGPR instead of reloading four
+//     spilled lane-mask pairs with v_readlane_b32.
+#ifndef PP2_RES_LEAN
+#define PP2_RES_LEAN 1
+#endif
+// (it builds on the one-round-trip window reads)
+#define PP2_RES_LEAN_ON (PP2_RES_LEAN != 0 && PP2_RES_WINDOW1 != 0)
+// The lean instances' four tile buffers: rows of xs = tw + 4 floats (4 pad
+// floats, then the row), buffer i's rows at row i (rt + 1) + 1 .., with a row
+// that is never written in front of every buffer and behind the last one.
+__host__ __device__ constexpr int lean_tile_floats(int rt, int tw) {
+  return 4 + (4 * (rt + 1) + 1) * (tw + 4);
+}
 // The gather of action U (belief_fact's support positions and ascending-s
 // order): an off-centre term is fmaf(w, window value, p) with the scalar
 // weight -- wm for the source cell that action U moves onto this one (T index
@@ -648,6 +681,27 @@ __device__ __forceinline__ void issue_window_rows(const float* const (&p)[NP], i
   } else {
     edges(lane < 32 ? -1 - 4 * lane : 4 + 4 * (63 - lane));
   }
+}
+// PP2_RES_LEAN: the same reads without a branch.  base + ro[k][r] is the start
+// of plane k's window row r (a wave-uniform offset: the tile row, or the row
+// of zeros), xq the lane's first cell and xe the edge cell of its half of the
+// wave (lanes 0..31: the wave's x - 1, lanes 32..63: its x + 256).  The order
+// is issue_window_rows': quads of rows 1, 0, 2, then the edge dwords of rows
+// 2, 1 and 0, plane 0 last.
+__device__ __forceinline__ void issue_window_rows_lean(const float* base, const int (&ro)[2][3],
+                                                       int xq, int xe, WinRows<2>& w) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) w.q[k][1] = *reinterpret_cast<const f4a*>(base + ro[k][1] + xq);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) w.q[k][0] = *reinterpret_cast<const f4a*>(base + ro[k][0] + xq);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) w.q[k][2] = *reinterpret_cast<const f4a*>(base + ro[k][2] + xq);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) w.e[k][2] = base[ro[k][2] + xe];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) w.e[k][1] = base[ro[k][1] + xe];
+#pragma unroll
+  for (int k = 1; k >= 0; --k) w.e[k][0] = base[ro[k][0] + xe];
 }
 // window row r from the quads and edge dwords in hand (row_lds's DPP moves)
 __device__ __forceinline__ void window_row(const f4a& m, float e, float (&v)[6]) {
@@ -876,7 +930,10 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   const int wp = a.g.wp, rows = a.g.rows, tw = wp / tc;
   const int tpr = tw >> 2, wpr = tw >> 8;  // lanes, waves per tile row
   const int xs = tw + 4;                // padded LDS row stride
-  const int bufn = 4 + a.rt * xs;       // one padded tile buffer
+  // (kLean: a buffer's rows and the never-written row in front of them,
+  // lean_tile_floats)
+  constexpr bool kLean = MSK && PP2_RES_LEAN_ON;
+  const int bufn = kLean ? (a.rt + 1) * xs : 4 + a.rt * xs;  // one padded tile buffer
   // LDS: class tables (QR, LT: constant offsets), factored sweep rows (QT, CT:
   // constant offsets; IW), class planes, b buffers 0, 1, J buffers 0, 1
   const int prows = a.rt + 2, ps = tw + 8;
@@ -886,7 +943,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   float* sB0 = reinterpret_cast<float*>(sP) + lds_span(MSK ? kResGCn : 9 * prows * ps / 4);
   const float* sGC = reinterpret_cast<const float*>(sP);
   (void)sGC;
-  float* sS = sB0 + 4 * bufn;
+  float* sS = sB0 + (kLean ? lean_tile_floats(a.rt, tw) : 4 * bufn);
   float* sRed = sS + 16;  // (red_lds) the lagged block start's partials
 
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -927,19 +984,34 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   const int sbase = 2 * a.ntiles * 2 * (wp >> 8) * kResidentGranules * 64 * 16;  // side region
   unsigned* const err = a.sync + kResidentSyncErr;
   const Rsrc rx = make_rsrc(a.xch);
-  auto sbuf = [&](int k, int slot) { return sB0 + (2 * k + slot) * bufn + 4; };
+  auto sbuf = [&](int k, int slot) { return sB0 + (2 * k + slot) * bufn + (kLean ? xs : 0) + 4; };
   // the boundary waves' hand-off: b and J of the lane's quad as two
   // self-tagged granules {b0..b3}, {j0..j3} in exchange slot `slot`
   // (whether the row granules' reader, tile -+ tc, shares this tile's XCD)
   const int myx = tile_xcd(tile, (int)gridDim.x);
   const bool plain_up = PP2_RES_XCD_PLAIN && nb_up && tile_xcd(tile - tc, (int)gridDim.x) == myx;
   const bool plain_dn = PP2_RES_XCD_PLAIN && nb_dn && tile_xcd(tile + tc, (int)gridDim.x) == myx;
+  // (kLean) the publish's role flags as bits of one SGPR: held as wave-uniform
+  // bools each is a lane-mask pair for the whole run, spilled, and the publish
+  // reloads them with v_readlane_b32 every step.  The empty asm keeps the
+  // compiler from widening a bit to such a mask again.  (The flags of the
+  // step's other branches stay bools: as bits they cost two VGPR spills in the
+  // backup, profiles/r12/README.txt.)
+  enum : unsigned { kRoleUp = 1, kRoleDn = 2, kRolePlainUp = 4, kRolePlainDn = 8 };
+  unsigned role = 0u;  // (set with bnd, below)
+  auto is = [&](unsigned bit, bool flag) {
+    if constexpr (kLean) {
+      asm volatile("" : "+s"(role));
+      return (role & bit) != 0u;
+    }
+    return flag;
+  };
   auto publish = [&](int slot, const float (&b)[4], const float (&j)[4], unsigned bit) {
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
-      if (side == 0 ? !nb_up : !nb_dn) continue;
+      if (side == 0 ? !is(kRoleUp, nb_up) : !is(kRoleDn, nb_dn)) continue;
       const int o = xch_gran(a.ntiles, wpr, slot, tile, side, wj, 0, lane);
-      const bool plain = side == 0 ? plain_up : plain_dn;
+      const bool plain = side == 0 ? is(kRolePlainUp, plain_up) : is(kRolePlainDn, plain_dn);
       st_quad_x(rx, o, b, bit, plain);
       st_quad_x(rx, o + 1024, j, bit, plain);
     }
@@ -997,6 +1069,36 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     }
   };
 
+  // (kLean) the same poll, the row's quads and edge dwords written over the
+  // window registers that issue_window_rows_lean filled from the row of zeros
+  auto take_q = [&](int slot, int tl, int side, unsigned bit, f4a& qb, float& eb, f4a& qj,
+                    float& ej) {
+    const bool el = lane == 0 && wj > 0, er = lane == 63 && wj + 1 < wpr;
+    const int o = xch_gran(a.ntiles, wpr, slot, tl, side, wj, 0, lane);
+    const int eo = el ? xch_gran(a.ntiles, wpr, slot, tl, side, wj - 1, 0, 63) + 12
+                      : xch_gran(a.ntiles, wpr, slot, tl, side, wj + 1, 0, 0);
+    u4v g[2];
+    unsigned e[2];
+    u2v s[3];
+    take_rows_sides(rx, true, o, el || er, eo, false, so, 0, bit, g, e, s, err, a.err_host);
+    // OR-ed over the +0 words read from the row of zeros (one v_and_or_b32
+    // each, as many as the untag alone): the registers' LDS reads stay in
+    // flight under the poll, which loads into registers of its own -- written
+    // as plain assignments the granules load straight into the window
+    // registers and the poll starts behind an LDS drain
+    auto over = [](float z, unsigned w, unsigned keep) {
+      return __uint_as_float(__float_as_uint(z) | (w & keep));
+    };
+    const unsigned ke = (el || er) ? 0x7fffffffu : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      qb[k] = over(qb[k], g[0][k], 0x7fffffffu);
+      qj[k] = over(qj[k], g[1][k], 0x7fffffffu);
+    }
+    eb = over(eb, e[0], ke);
+    ej = over(ej, e[1], ke);
+  };
+
   // ---- prologue: dictionary, zero pads, codes, the tile's b / J into LDS
   // buffer 0, boundary rows into exchange slot 1 (as if step -1's output),
   // then the neighbours' rows for step 0.
@@ -1036,9 +1138,15 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   stage_rows(a.rfact, kResTab, lds);
   stage_rows(a.rows, rows_floats(a.E, true), sTC);
   if constexpr (MSK) stage_rows(a.rfact + kResGC, kResGCn, reinterpret_cast<float*>(sP));
-  for (int i = threadIdx.x; i < 4 * (a.rt + 1); i += blockDim.x) {
+  // (kLean: every float of the buffers -- the pads, the rows between the
+  // buffers and a partial tile's rows below the grid, which no wave writes)
+  for (int i = threadIdx.x; !kLean && i < 4 * (a.rt + 1); i += blockDim.x) {
     const int buf = i / (a.rt + 1), r = i % (a.rt + 1);
     *reinterpret_cast<f4a*>(sB0 + buf * bufn + r * xs) = f4a{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  if constexpr (kLean) {
+    for (int i = threadIdx.x; 4 * i < lean_tile_floats(a.rt, tw); i += blockDim.x)
+      *reinterpret_cast<f4a*>(sB0 + 4 * i) = f4a{0.0f, 0.0f, 0.0f, 0.0f};
   }
   // the lane's cells: codes, their IW records (registers for the whole run)
   // and L class bytes
@@ -1125,6 +1233,10 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   }
   if (prior_err != 0u) return;  // (uniform: before any global store)
   const bool bnd = nb_up || nb_dn || sd_l || sd_r;  // waves that cross CUs
+  if constexpr (kLean)
+    role = (unsigned)__builtin_amdgcn_readfirstlane(
+        (int)((nb_up ? kRoleUp : 0u) | (nb_dn ? kRoleDn : 0u) | (plain_up ? kRolePlainUp : 0u) |
+              (plain_dn ? kRolePlainDn : 0u)));
   if (valid) {
     f4a b = b_t, j = j_t;
     if constexpr (MSK) {  // blocked cells as +0 in the planes and the granules
@@ -1244,6 +1356,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   (void)trw;
   (void)uzw;
   (void)ph;
+  // (kLean) the edge cell of the lane's half of the wave (issue_window_rows_lean)
+  const int xe = kLean ? wj * 256 + (lane < 32 ? -1 : 256) : 0;
+  (void)xe;
   for (int t = 0; t < a.n; ++t) {
 #if PP2_RES_TRAJ_SGPR
     const uint32_t uzb = (uzw >> (8 * (t & 3))) & 0xffu;
@@ -1366,6 +1481,10 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       asm volatile("" ::: "memory");
 #endif
     };
+    // (kLean) the step's masked J quad, best * mk: stored by step_quad,
+    // published by finish_quad
+    float jmq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    (void)jmq;
     // one quad of step t: window rows from LDS (step t-1), the neighbour rows
     // of step t-1, or 0 off the grid; b' before the scale in p
     auto step_quad = [&]() {
@@ -1410,7 +1529,30 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         else masked_sweep_pipe_begin<4, false>(sGC, iwr, mrec);
       }
 #if PP2_RES_WINDOW1 != 0
-      if constexpr (kSweepPipe) {
+      if constexpr (kLean) {
+        // the same burst without a branch or a select: rows ty - 1 and ty + 1
+        // of a buffer are there for every wave -- a tile row, or zeros (the row
+        // in front of the buffer, the one behind it, a partial tile's row
+        // below the grid) -- and a neighbour's granules land in the registers
+        // that read the zeros
+        int ro[2][3];
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int r = 0; r < 3; ++r) ro[k][r] = (2 * k + ci) * bufn + 4 + (ty + r) * xs;
+        WinRows<2> wr;
+        issue_window_rows_lean(sB0, ro, x0, xe, wr);
+        __builtin_amdgcn_sched_barrier(0);
+        if (nb_up)  // the tile above's last row
+          take_q(co, tile - tc, 1, bit, wr.q[0][0], wr.e[0][0], wr.q[1][0], wr.e[1][0]);
+        if (nb_dn)  // the tile below's first row
+          take_q(co, tile + tc, 0, bit, wr.q[0][2], wr.e[0][2], wr.q[1][2], wr.e[1][2]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          window_row(wr.q[0][r], wr.e[0][r], wb.v[r]);
+          window_row(wr.q[1][r], wr.e[1][r], wj.v[r]);
+        }
+      } else if constexpr (kSweepPipe) {
         // every LDS read of the window rows issued here, behind the class
         // dwords and the records and before a neighbour's poll; the DPP moves
         // (window_row) consume them after it
@@ -1517,7 +1659,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         for (int k = 0; k < 4; ++k) {
           const bool blocked = mk[k] == 0.0f;
           best[k] = blocked ? ov[k] : best[k];
-          arg[k] = blocked ? 0u : arg[k];
+          if (!kLean || last) arg[k] = blocked ? 0u : arg[k];  // (stored by the last step alone)
+        }
+        if constexpr (kLean) {  // (finish_quad publishes the same quad)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) jmq[k] = best[k] * mk[k];
+          *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) = f4a{jmq[0], jmq[1], jmq[2], jmq[3]};
+          return;
         }
         *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) =
             f4a{best[0] * mk[0], best[1] * mk[1], best[2] * mk[2], best[3] * mk[3]};
@@ -1544,7 +1692,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         const float pm[4] = {p[0] * mk[0], p[1] * mk[1], p[2] * mk[2], p[3] * mk[3]};
         *reinterpret_cast<f4a*>(sbuf(0, co) + ty * xs + x0) = f4a{pm[0], pm[1], pm[2], pm[3]};
         if (bnd) {
-          const float jm[4] = {best[0] * mk[0], best[1] * mk[1], best[2] * mk[2], best[3] * mk[3]};
+          float jm[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) jm[k] = kLean ? jmq[k] : best[k] * mk[k];
           if (!last) publish(ci, pm, jm, (use[ci] + 1u) & 1u);
           __builtin_amdgcn_s_setprio(0);
         }
@@ -1575,7 +1725,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         if (lane == 0) sS[0] = S;
       }
       __syncthreads();
-      if (a.shard) {
+      if (!kLean && a.shard) {  // (the masked launch is never a shard's)
         const int sh = pow2_shift(sS[0]);
         shift += sh;
         inv = pow2f(sh);
@@ -1880,7 +2030,9 @@ size_t resident_lds_bytes(const Geom& g, int E, int rt, int tc) {
 
 size_t resident_masked_lds_bytes(const Geom& g, int E, int rt) {
   return ((size_t)lds_span(kResTab) + lds_span(rows_floats(E, true)) + lds_span(kResGCn) +
-          4 * (4 + (size_t)rt * (g.wp + 4)) + 16) *
+          (PP2_RES_LEAN_ON ? (size_t)lean_tile_floats(rt, g.wp)
+                                                     : 4 * (4 + (size_t)rt * (g.wp + 4))) +
+          16) *
          sizeof(float);
 }
 
