@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pp2.h"
+#include "pp2_dict_props.h"
 #include "pp2_internal.h"
 
 using pp2::Geom;
@@ -131,7 +132,15 @@ struct pp2_ctx {
   pp2::ResidentMasked res_mw{};    // ... its weights
   // the sparse rows' T == 0 skip needs finite, non-negative beliefs (not -0):
   // false after a pp2_belief_set that breaks that, until the next one
+  // ... and after a belief update under a model whose T or L breaks it
+  // (pp2_dict_props.h: the state rule); values_sparse_ok likewise for J,
+  // set by pp2_mdp_reset, cleared by a sweep under a model whose T or C does
   bool belief_sparse_ok = true;
+  bool values_sparse_ok = true;
+  pp2::DictProps dict_props{};     // the last dictionary's scalar properties
+  // every T / L / C entry of the model in force finite and >= +0 (C: and the
+  // gamma bound); from the dictionary, else from a scan of the uploaded planes
+  bool model_t_ok = false, model_l_ok = false, model_c_ok = false;
   bool use_coded = true;           // PP2_TUNE_CODED_MODEL
   // control selection (pp2_control.cpp), allocated on first use: Q partials
   // [blocks][9] and mode partials (value, index)[blocks] on the device, and

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "pp2_ctx.h"
+#include "pp2_dict_props.h"
 #include "pp2_masked.h"
 
 using pp2::Geom;
@@ -379,8 +380,38 @@ std::string join(const char* dir, const char* name) {
   return d + name;
 }
 
-bool coded_active(const pp2_ctx* c) {
-  return c->use_coded && c->dict_n > 0 && c->cpt == 4 && (!c->dict_sparse || c->belief_sparse_ok);
+// The path gates are pp2_dict_props.h's, on the last dictionary's properties
+// and these switches and state flags.
+static pp2::GateCtx gate_ctx(const pp2_ctx* c) {
+  pp2::GateCtx x;
+  x.resident = c->resident != 0;
+  x.use_coded = c->use_coded;
+  x.cpt = c->cpt;
+  x.norm_block = c->norm_block;
+  x.sharded = c->comm || c->group;
+  x.ncus = c->ncus;
+  x.entries = c->dict_n;
+  x.belief_ok = c->belief_sparse_ok;
+  x.values_ok = c->values_sparse_ok;
+  return x;
+}
+
+bool coded_active(const pp2_ctx* c) { return pp2::gate_coded_active(c->dict_props, gate_ctx(c)); }
+
+// The state rule of pp2_dict_props.h: a belief update (values: a sweep) that
+// runs under a model failing the beliefs (values) condition clears the
+// state's flag before it is launched, so it and everything after it stay off
+// the sparse rows and the resident kernels until pp2_belief_set /
+// pp2_mdp_reset.
+static void note_belief_step(pp2_ctx* c) {
+  if (!(c->model_t_ok && c->model_l_ok)) c->belief_sparse_ok = false;
+}
+static void note_value_sweep(pp2_ctx* c) {
+  if (!(c->model_t_ok && c->model_c_ok)) c->values_sparse_ok = false;
+}
+static void note_loop_step(pp2_ctx* c) {
+  note_belief_step(c);
+  note_value_sweep(c);
 }
 
 // pp2_masked.h restates the base kernels' supports (it includes no HIP header)
@@ -393,13 +424,11 @@ static constexpr bool masked_supports_agree() {
   return true;
 }
 static_assert(masked_supports_agree(), "pp2_masked.h: kSup / kSupN");
-
-// +0 <= v < +inf (sign bit clear, not inf or NaN)
-static bool finite_nonneg(float v) {
-  uint32_t bits;
-  std::memcpy(&bits, &v, 4);
-  return bits < 0x7f800000u;
-}
+static_assert(pp2::props_detail::kFactK == pp2::kFactK && pp2::props_detail::kLK == pp2::kResLK &&
+                  pp2::props_detail::kL == pp2::kDictL &&
+                  pp2::props_detail::kRing == pp2::kResidentRing,
+              "pp2_dict_props.h: the restated constants");
+using pp2::finite_nonneg;
 
 // Dictionary of the distinct per-cell model tuples (T, C, L) over rows
 // [-1, rows]: GPU hash per cell, first-appearance numbering on the host, GPU
@@ -416,6 +445,9 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
                      const Planes* mC) {
   c->dict_n = 0;
   c->dict_masked = false;
+  c->dict_props = pp2::DictProps{};
+  // (no dictionary: the callers judge the model, pp2_model_generate / _upload)
+  c->model_t_ok = c->model_l_ok = c->model_c_ok = false;
   c->res_e_dict = -1;  // shard_resident_e: recomputed (collectively) on the next run
   ++c->agree_gen;      // ... and agreed again (pp2_loop_run)
   const long long n = (long long)(c->g.rows + 2 * c->g.halo) * c->g.wp;
@@ -488,48 +520,15 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
                         c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (bad) return PP2_OK;
-  bool t_finite = true;
-  for (int e = 0; e < E && t_finite; ++e)
-    for (int a = 0; a < 9; ++a)
-      for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(dh[(size_t)e * pp2::kDictRow + a * 10 + i])) t_finite = false;
-  // the resident kernels hand over beliefs and values with a tag bit in the
-  // sign bit: every T and L entry finite and >= +0 keeps every belief so
-  // (values: C >= +0, the sparse rows' precondition below)
-  bool tl_nonneg = true;
-  for (int e = 0; e < E && tl_nonneg; ++e) {
-    for (int a = 0; a < 9; ++a)
-      for (int i = 0; i < 9; ++i)
-        if (!finite_nonneg(dh[(size_t)e * pp2::kDictRow + a * 10 + i])) tl_nonneg = false;
-    for (int z = 0; z < 16; ++z)
-      if (!finite_nonneg(dh[(size_t)e * pp2::kDictRow + pp2::kDictL + z])) tl_nonneg = false;
-  }
-  // LDS-layout rows: sparse when every T entry off the base-kernel support is
-  // +0.0 (always so for generated models), else the full [a][T..,C] rows
-  // They also drop the T == 0 terms of the Bellman backup, which equals the
-  // dense fmaf chain only while every partial cost stays finite and never -0:
-  // every dictionary C finite and >= +0 (J then starts at +0 and stays finite
-  // below max C / (1 - gamma)), 0 <= gamma < 1.  Otherwise the full rows
-  // (no term dropped) keep coded == dense bit for bit.
+  // The scalar properties and the path gates: pp2_dict_props.h.  LDS-layout
+  // rows: sparse (factored) when every T entry off the base-kernel support is
+  // +0.0 and the model keeps J finite and >= +0 (always so for generated
+  // models), else the full [a][T..,C] rows (no term dropped), which keep
+  // coded == dense bit for bit on any model.
   const float gam = c->gamma;
-  bool sparse = gam >= 0.0f && gam < 1.0f;
-  double cmax = 0.0;
-  for (int e = 0; e < E && sparse; ++e)
-    for (int a = 0; a < 9; ++a) {
-      const float cv = dh[(size_t)e * pp2::kDictRow + a * 10 + 9];
-      if (!finite_nonneg(cv)) { sparse = false; break; }
-      cmax = std::max(cmax, (double)cv);
-    }
-  if (sparse && cmax / (1.0 - (double)gam) >= 0.5 * (double)FLT_MAX) sparse = false;
-  for (int e = 0; e < E && sparse; ++e)
-    for (int a = 0; a < 9 && sparse; ++a)
-      for (int i = 0; i < 9; ++i) {
-        bool in = false;
-        for (int j = 0; j < pp2::kSupN[a]; ++j) in |= pp2::kSup[a][j] == i;
-        uint32_t bits;
-        std::memcpy(&bits, &dh[(size_t)e * pp2::kDictRow + a * 10 + i], 4);
-        if (!in && bits != 0) { sparse = false; break; }
-      }
+  const pp2::DictProps props = pp2::dict_props(dh.data(), E, pp2::kDictRow, gam);
+  const bool t_finite = props.t_finite, tl_nonneg = props.tl_nonneg();
+  bool sparse = props.sparse();
   // Factored sweep rows (pp2_internal.h): per action the distinct (gT support
   // quad, C_a) pairs, at most kFactK of them, else the full rows.  The classes
   // are keyed on the raw T quad as well, so that a class also fixes the belief
@@ -586,8 +585,8 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
   // and the base kernel's two weights (gamma * w rounded once, as fact_qt).
   bool masked = false;
   pp2::ResidentMasked mw{};
-  if (rfact_ok && tl_nonneg && t_finite && c->g.halo >= 1 && c->g.row0 == 0 &&
-      c->g.grows == c->g.rows) {
+  if (rfact_ok && pp2::gate_masked_precheck(props, c->g.halo >= 1 && c->g.row0 == 0 &&
+                                                          c->g.grows == c->g.rows)) {
     const pp2::MaskedModel mm =
         pp2::masked_admit(code.data() + (size_t)(c->g.halo - 1) * c->g.wp, c->g.wp, c->g.rows,
                           dh.data(), E, pp2::kDictRow, gam);
@@ -656,11 +655,16 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
   c->dict_masked = masked;
   c->res_mw = mw;
   c->dict_n = E;
+  c->dict_props = props;
+  c->model_t_ok = props.t_nonneg;
+  c->model_l_ok = props.l_nonneg;
+  c->model_c_ok = props.cost_ok;
   return PP2_OK;
 }
 
 int mdp_sweep_once(pp2_ctx* c) {
   const int jn = c->jcur ^ 1;
+  note_value_sweep(c);
   break_pipeline(c);  // the deep halo rows of J are stale after a sweep
   if (coded_active(c)) {
     HIPCHK(pp2::launch_mdp_sweep_coded(c->stream, c->g, c->gamma, c->d_code, c->d_rows,
@@ -732,6 +736,7 @@ void pp2rt::break_pipeline(pp2_ctx* c) { c->kstep = 0; }
 // k_belief_update -- the same arithmetic and partial layout either way.
 int pp2rt::launch_belief(pp2_ctx* c, const float* b_in, float* b_out, uint8_t u, uint8_t z,
                          const float* mass, float* partials) {
+  note_belief_step(c);
   if (coded_active(c)) {
     HIPCHK(pp2::launch_loop_step_coded(
         c->stream, c->g, c->gamma, c->d_code, c->d_rows,
@@ -752,6 +757,7 @@ int pp2rt::belief_update_impl(pp2_ctx* c, uint8_t u, uint8_t z, bool fuse_with_s
   if (u > 8 || z > 15) return set_err(PP2_EINVAL, "action %u / observation %u out of range", u, z);
   CHECK(ensure_mass(c));
   break_pipeline(c);
+  note_belief_step(c);
   const int bn = c->bcur ^ 1;
   const int nparts = pp2::mass_partials(c->g, c->cpt);
   CHECK(launch_belief(c, c->b[c->bcur].v.p, c->b[bn].v.p, u, z, c->bsum + c->bcur, c->pbuf[bn]));
@@ -786,6 +792,7 @@ int pp2rt::loop_launch(pp2_ctx* c, int e, uint8_t u, uint8_t z, const float* in_
   const float* J_in = c->J[jc].v.p - e * wp;
   float* J_out = c->J[jn].v.p - e * wp;
   uint8_t* A = c->A - e * wp;  // only owned rows are stored
+  note_loop_step(c);
   if (coded_active(c)) {
     HIPCHK(pp2::launch_loop_step_coded(c->stream, g, c->gamma, c->d_code - e * wp, c->d_rows,
                                        c->d_dl + (size_t)z * ((c->dict_n + 3) & ~3),
@@ -811,6 +818,7 @@ int pp2rt::loop_step_fused(pp2_ctx* c, uint8_t u, uint8_t z, bool eager_mass) {
   if (u > 8 || z > 15) return set_err(PP2_EINVAL, "action %u / observation %u out of range", u, z);
   const int bc = c->bcur, bn = bc ^ 1, jn = c->jcur ^ 1;
   const bool pend = c->pending[bc];
+  note_loop_step(c);
   int nparts = 0;
   CHECK(loop_launch(c, 0, u, z, pend ? c->pbuf[bc] : nullptr, c->pcount[bc], c->bsum + bc,
                     pend ? c->bsum + bc : nullptr, &nparts));
@@ -837,6 +845,7 @@ static int blocked_loop_step(pp2_ctx* c, uint8_t u, uint8_t z) {
   const int depth = shard ? c->kdepth : c->norm_block;
   const int bc = c->bcur, bn = bc ^ 1, jn = c->jcur ^ 1;
   const bool start = c->kstep == 0;
+  note_loop_step(c);
   // unsharded coded context: a pending mass is reduced inside the block-start
   // launch (stored to bsum[bc]) instead of by a separate k_sum_finalize
   const bool fold = start && !shard && c->pending[bc] && coded_active(c);
@@ -865,7 +874,10 @@ static int blocked_loop_step(pp2_ctx* c, uint8_t u, uint8_t z) {
 // one row deeper from the halo.
 bool pp2rt::pairs_apply(pp2_ctx* c) {
   const int depth = (c->comm || c->group) ? c->kdepth : c->norm_block;
+  // (the pair's second step reads the first one's b and J through the sparse
+  // rows: only under a model that keeps both finite and >= +0)
   return c->step_pairs && depth >= 2 && coded_active(c) && c->dict_sparse &&
+         c->model_t_ok && c->model_l_ok && c->model_c_ok &&
          pp2::loop_pair_fits(c->g, c->dict_n, true) &&
          (c->step_pairs == 2 || pp2::loop_pair_pays(c->g));
 }
@@ -1023,9 +1035,7 @@ static Geom view_geom(const pp2_ctx* c, int e) {
 // finite T (the kernel's zero-padded edges multiply T by +0) and the class
 // tables.
 static bool resident_model_ok(const pp2_ctx* c) {
-  return c->resident && coded_active(c) && c->dict_sparse && c->dict_t_finite &&
-         c->dict_tl_nonneg && c->dict_rfact &&
-         c->norm_block <= pp2::kResidentRing - 2 && c->ncus > 0;
+  return c->dict_rfact && pp2::gate_resident_model(c->dict_props, gate_ctx(c));
 }
 
 // Whether a loop plan exists for view extension e (0: an unsharded grid),
@@ -1055,9 +1065,9 @@ static bool resident_ready(pp2_ctx* c) {
 // Whether pp2_mdp_solve runs as resident sweeps (k_sweep_resident): the
 // resident loop's conditions minus the belief's, and a plan for J alone.
 static bool solve_plan_ok(pp2_ctx* c) {
-  if (!c->resident || c->comm || c->group || !coded_active(c) || !c->dict_sparse ||
-      c->ncus <= 0)  // (values >= +0 finite: the sparse rows' precondition)
-    return false;
+  // (values finite and >= +0: every T and C entry so, and J not carried over
+  // from a model that broke it -- pp2_dict_props.h)
+  if (!c->dict_sparse || !pp2::gate_sweep_resident(c->dict_props, gate_ctx(c))) return false;
   if (c->sol_plan_e != c->dict_n) {
     c->sol_plan_e = c->dict_n;
     c->sol_ok = false;
@@ -1862,6 +1872,14 @@ int pp2_set_cells_per_lane(pp2_ctx* c, int cpt) {
 }
 
 // ---------------------------------------------------------------- model
+// A generated model has every T, L and C entry finite and >= +0 (C <= 5);
+// without a dictionary (a hash collision) nothing has scanned it.
+static void generated_model_flags(pp2_ctx* c) {
+  if (c->dict_n > 0) return;
+  c->model_t_ok = c->model_l_ok = true;
+  c->model_c_ok = pp2::gamma_bound_ok(c->gamma, 5.0);
+}
+
 int pp2_model_generate(pp2_ctx* c) {
   CHECK(check_ctx(c));
   DeviceGuard dg(c->device);
@@ -1869,7 +1887,9 @@ int pp2_model_generate(pp2_ctx* c) {
     HIPCHK(pp2::launch_model_gen(c->stream, c->g, c->d_map, c->gx, c->gy, c->T.v,
                                  c->L.v, c->R.v, c->C.v));
     c->model_ready = true;
-    return build_model_dict(c);
+    const int s = build_model_dict(c);
+    if (s == PP2_OK) generated_model_flags(c);
+    return s;
   }
   // A shard with deep halo rows: the model over rows [-g.halo, rows +
   // g.halo) into a transient full-halo copy, the code plane built from it,
@@ -1894,6 +1914,7 @@ int pp2_model_generate(pp2_ctx* c) {
   c->model_ready = true;
   const int s = build_model_dict(c, &t[0], &t[1], &t[2], &t[3]);
   HIPCHK(hipStreamSynchronize(c->stream));  // (before the transient planes go)
+  if (s == PP2_OK) generated_model_flags(c);
   return s;
 }
 
@@ -1927,7 +1948,22 @@ int pp2_model_upload(pp2_ctx* c, const float* T, const float* L, const float* R,
   if (R) CHECK(upload_planes(c, c->R, R));
   if (C) CHECK(upload_planes(c, c->C, C));
   c->model_ready = true;
-  if (c->dense_halo >= c->g.halo) return build_model_dict(c);
+  // Without a dictionary (too many distinct cells) the model's conditions
+  // (pp2_dict_props.h) come from the planes given here, and from the previous
+  // model for the others.
+  const bool prev[3] = {c->model_t_ok, c->model_l_ok, c->model_c_ok};
+  auto judge = [&](int s) {
+    if (s != PP2_OK || c->dict_n > 0) return s;
+    const size_t n = owned_cells(c);
+    double cmax = 0.0;
+    c->model_t_ok = T ? pp2::plane_finite_nonneg(T, n * 81, nullptr) : prev[0];
+    c->model_l_ok = L ? pp2::plane_finite_nonneg(L, n * 16, nullptr) : prev[1];
+    c->model_c_ok = C ? pp2::plane_finite_nonneg(C, n * 9, &cmax) &&
+                            pp2::gamma_bound_ok(c->gamma, cmax)
+                      : prev[2];
+    return s;
+  };
+  if (c->dense_halo >= c->g.halo) return judge(build_model_dict(c));
   // A whole-grid shard context (rows == grows, its own RCCL rank or none):
   // its dense planes hold dense_halo < g.halo halo rows, but the dictionary
   // build walks rows [-g.halo, rows + g.halo).  Build it from transient
@@ -1949,7 +1985,7 @@ int pp2_model_upload(pp2_ctx* c, const float* T, const float* L, const float* R,
   }
   const int s = build_model_dict(c, &t[0], &t[1], &t[2], &t[3]);
   HIPCHK(hipStreamSynchronize(c->stream));  // (before the transient planes go)
-  return s;
+  return judge(s);
 }
 
 int pp2_model_save(pp2_ctx* c, const char* dir) {
@@ -1982,10 +2018,16 @@ int pp2_belief_set(pp2_ctx* c, const float* b) {
   ++c->agree_gen;  // (after a lost shard run: every rank agrees again)
   DeviceGuard dg(c->device);
   break_pipeline(c);
+  // the pad columns of the owned rows as well: the kernels compute the pad
+  // lanes from their own stale word (0 * NaN, 0 * -x), and the resident loop
+  // hands a tile's whole edge row over -- a NaN or -0 that a non-finite or
+  // negative belief left there must not outlive it (pp2_dict_props.h)
+  HIPCHK(hipMemsetAsync(c->b[c->bcur].v.p, 0,
+                        (size_t)c->g.rows * c->b[c->bcur].v.rs * sizeof(float), c->stream));
   CHECK(upload_planes(c, c->b[c->bcur], b));
   bool ok = true;
   for (size_t i = 0; i < (size_t)c->g.rows * c->g.width && ok; ++i) ok = finite_nonneg(b[i]);
-  c->belief_sparse_ok = ok;
+  c->belief_sparse_ok = ok;  // (cleared again by a step under a model that breaks it)
   c->pending[c->bcur] = false;
   const float one = 1.0f;
   HIPCHK(hipMemcpyAsync(c->bsum + c->bcur, &one, sizeof one, hipMemcpyHostToDevice, c->stream));
@@ -2036,6 +2078,7 @@ int pp2_mdp_reset(pp2_ctx* c) {
     HIPCHK(hipMemsetAsync(P->alloc, 0, P->floats * sizeof(float), c->stream));
   HIPCHK(hipMemsetAsync(c->A, 0, (size_t)c->g.rows * c->g.wp, c->stream));
   c->jcur = 0;
+  c->values_sparse_ok = true;  // J = +0 (cleared again by a sweep under a model that breaks it)
   break_pipeline(c);
   c->lost_values = false;  // only once the values are reset
   return PP2_OK;
