@@ -19,32 +19,10 @@ import numpy as np
 import pytest
 
 from conftest import GAMMA, golden, golden_map
+# (the snapshot comparisons are shared with test_gpu_planner_shapes.py)
+from planner_shape_cases import compare, compare_exact, rel_close
 
 pytestmark = pytest.mark.gpu
-
-
-def rel_close(a, b, rel=1e-5, atol=1e-6):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return np.all(np.abs(a - b) <= np.maximum(rel * np.abs(b), atol))
-
-
-def compare(gi, oi, where, rel=1e-5):
-    for k in ("depth", "expansions", "n_root_children", "total_vnodes", "total_qnodes"):
-        assert gi[k] == oi[k], f"{where}: {k} {gi[k]} != {oi[k]}"
-    n = gi["n_root_children"]
-    assert np.array_equal(gi["q_nchildren"][:n], oi["q_nchildren"][:n]), where
-    assert np.array_equal(gi["q_depth"][:n], oi["q_depth"][:n]), where
-    for a in range(n):
-        m = gi["q_nchildren"][a]
-        assert np.array_equal(gi["q_obs"][a][:m], oi["q_obs"][a][:m]), where
-        assert np.array_equal(gi["q_weight"][a][:m], oi["q_weight"][a][:m]), where
-        assert rel_close(gi["v_upper_bound"][a][:m], oi["v_upper_bound"][a][:m], rel), where
-        assert rel_close(gi["v_lower_bound"][a][:m], oi["v_lower_bound"][a][:m], rel), where
-    for k in ("q_upper_bound", "q_lower_bound", "q_reward", "q_heuristic"):
-        assert rel_close(gi[k][:n], oi[k][:n], rel), f"{where}: {k}"
-    for k in ("root_upper_bound", "root_lower_bound", "root_heuristic"):
-        assert rel_close(gi[k], oi[k], rel), f"{where}: {k}"
 
 
 @pytest.mark.parametrize("name,max_depth,max_iter,steps", [
@@ -210,19 +188,6 @@ def test_planner_pbvi_lower_bound(oracle, name, S, max_depth, steps):
                 compare(gpl.info(), opl.info(), f"{name} pbvi step {k + 1}")
                 assert a_g == a_o and rel_close(v_g, v_o)
     opl.close()
-
-
-def compare_exact(gi, oi, where):
-    """Every field of the two tree snapshots equal (floats bit for bit)."""
-    for k in gi:
-        a, b = np.asarray(gi[k]), np.asarray(oi[k])
-        if a.dtype.kind == "f":
-            a32 = np.atleast_1d(a.astype(np.float32))
-            b32 = np.atleast_1d(b.astype(np.float32))
-            assert np.array_equal(a32.view(np.uint32), b32.view(np.uint32)), \
-                f"{where}: {k} {a} != {b}"
-        else:
-            assert np.array_equal(a, b), f"{where}: {k} {a} != {b}"
 
 
 @pytest.mark.parametrize("name,max_depth,lb,S,steps,seq_max,walk", [
