@@ -214,6 +214,12 @@ int pp2_set_cells_per_lane(pp2_ctx* ctx, int cpt);
  *                           events on the stream it runs on; read with
  *                           pp2_comm_rounds.  0 (default) = no events. */
 #define PP2_TUNE_COMM_TIMING 14
+/*  PP2_TUNE_MAP_INCREMENTAL 1 (default): pp2_map_update / pp2_goal_set
+ *                           regenerate and re-code only the cells that changed.
+ *                           0 = every update regenerates the whole model and
+ *                           rebuilds the dictionary.  Results are identical
+ *                           either way. */
+#define PP2_TUNE_MAP_INCREMENTAL 16
 int pp2_set_tuning(pp2_ctx* ctx, int key, int value);
 /* Measurement, no reference counterpart (the reference is single-GPU): the
  * RCCL rounds timed since PP2_TUNE_COMM_TIMING was set or the last call --
@@ -250,6 +256,60 @@ int pp2_model_load(pp2_ctx* ctx, const char* dir);
  * only); active = 1 when pp2_loop_step / pp2_mdp_sweep use it.  Results are
  * bit-identical either way. */
 int pp2_model_dict_info(pp2_ctx* ctx, int* entries, int* active);
+
+/* ---------------------------------------------------------------- live updates
+ * No reference counterpart (the reference fixes map and goal at start-up).
+ * Unsharded contexts only: a row shard, an RCCL rank or a shard-group member
+ * returns PP2_ESTATE.
+ *
+ * pp2_map_update: rows [y0, y0 + h) x columns [x0, x0 + w) of the stored map
+ * take `patch` (h * w bytes, row-major, pp2_create's meaning: 1 = occupied,
+ * anything else free).  PP2_EINVAL for an empty rectangle, one that leaves the
+ * grid, or a null patch.  Stream ordered like pp2_model_generate.
+ * pp2_goal_set: the goal becomes (gx, gy) -- any integers, as for pp2_create;
+ * off the grid means no goal cell.
+ *
+ * Before a model exists both only rewrite the stored map / goal.  With a
+ * generated model in force (made by pp2_model_generate and kept so by these
+ * calls) they leave the context exactly as a freshly created context with the
+ * new map and goal would be after pp2_model_generate:
+ *   - T, L, R and C have the fresh context's bits;
+ *   - the coded model is active under the same conditions;
+ *   - the masked-support admission (pp2_resident_masked) is the one a fresh
+ *     build decides;
+ *   - the dictionary's entry numbering may differ from a fresh build and rows
+ *     that no cell uses any more may remain (pp2_model_dict_info's entry count
+ *     may be larger); no result depends on either.
+ * A cell's model is a function of its 3x3 occupancy and of being the goal, so
+ * a w x h rectangle regenerates at most (w + 2) x (h + 2) cells and a goal move
+ * two; each is re-coded against the dictionary in force, new tuples append
+ * rows.  Anything the patch path cannot settle (a hash collision, more than
+ * the dictionary's row limit) runs the full build instead: correctness never
+ * rests on the fast path (PP2_TUNE_MAP_INCREMENTAL 0 always takes the full one).
+ * With an uploaded or loaded model in force they return PP2_ESTATE:
+ * regenerating part of a foreign model would mix two models.
+ *
+ * The belief, J / A, the FIB alphas, the PBVI beliefs and alphas and every
+ * tuning setting are state: kept untouched -- the caller re-solves
+ * (pp2_mdp_resolve, pp2_fib_solve, ...).  A generated model is clean, so the
+ * state flags of the sparse paths are neither cleared nor set.  Objects that
+ * cached model data at creation refuse to run afterwards: pp2_planner_step of
+ * a planner created before an update that changed the model returns
+ * PP2_ESTATE (create a new one); rollouts and episode batches read the model
+ * on every run and carry on. */
+int pp2_map_update(pp2_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                   const uint8_t* patch);
+int pp2_goal_set(pp2_ctx* ctx, int32_t gx, int32_t gy);
+/* The map (height * width bytes, as given) and goal in force; any pointer may
+ * be NULL. */
+int pp2_map_get(pp2_ctx* ctx, uint8_t* map, int32_t* gx, int32_t* gy);
+/* Diagnostics: update calls that changed the model, those of them served by
+ * the patch path, those that ran the full build (PP2_TUNE_MAP_INCREMENTAL 0,
+ * or a fall-back), and the dictionary rows the last such call appended.  A
+ * call that changes no cell's occupancy (or moves no goal cell) counts
+ * nowhere.  Any pointer may be NULL. */
+int pp2_map_update_info(pp2_ctx* ctx, long long* updates, long long* incremental,
+                        long long* rebuilds, int* entries_added);
 
 /* Loop steps pp2_loop_run fuses into one kernel launch on this context: 2048
  * for the tile-resident loop (PP2_TUNE_RESIDENT) on an unsharded grid, the
@@ -310,6 +370,12 @@ int pp2_mdp_sweep(pp2_ctx* ctx, int n);
  * change over a block is <= 1e-3*5/(1-gamma).  max_sweeps <= 0: no cap. */
 int pp2_mdp_solve(pp2_ctx* ctx, int max_sweeps, int* sweeps,
                   double* final_norm);
+/* pp2_mdp_solve without its pp2_mdp_reset: the same driver, stop rule and
+ * resident path, started from the current J (after pp2_map_update /
+ * pp2_goal_set: the previous solution).  If a resident launch times out it
+ * falls back as pp2_mdp_solve does, which restarts from J = 0. */
+int pp2_mdp_resolve(pp2_ctx* ctx, int max_sweeps, int* sweeps,
+                    double* final_norm);
 /* D2H of dev_optimal_cost1 / dev_optimal_action
  * (src/mdp/path_planning_2d.cu:119-126).  Either may be NULL. */
 int pp2_mdp_get(pp2_ctx* ctx, float* J, uint8_t* A);

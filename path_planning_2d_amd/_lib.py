@@ -60,6 +60,11 @@ SIGNATURES = {
     "pp2_model_save": [_vp, C.c_char_p],
     "pp2_model_load": [_vp, C.c_char_p],
     "pp2_model_dict_info": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "pp2_map_update": [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u8p],
+    "pp2_goal_set": [_vp, C.c_int32, C.c_int32],
+    "pp2_map_get": [_vp, _u8p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "pp2_map_update_info": [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                            C.POINTER(C.c_longlong), C.POINTER(C.c_int)],
     "pp2_loop_steps_per_launch": [_vp, C.POINTER(C.c_int)],
     "pp2_resident_tiling": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pp2_resident_launches": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -73,6 +78,7 @@ SIGNATURES = {
     "pp2_mdp_reset": [_vp],
     "pp2_mdp_sweep": [_vp, C.c_int],
     "pp2_mdp_solve": [_vp, C.c_int, _i32p, _f64p],
+    "pp2_mdp_resolve": [_vp, C.c_int, _i32p, _f64p],
     "pp2_mdp_get": [_vp, _f32p, _u8p],
     "pp2_loop_step": [_vp, C.c_uint8, C.c_uint8],
     # trajectories go in as bytes objects (c_char_p: a pointer to their

@@ -109,6 +109,7 @@ class GridContext:
     TUNE_SHARD_LAG = 13
     TUNE_COMM_TIMING = 14
     TUNE_RESIDENT_MASKED = 15
+    TUNE_MAP_INCREMENTAL = 16
 
     def set_tuning(self, key: int, value: int):
         call("pp2_set_tuning", self._h, int(key), int(value))
@@ -133,6 +134,40 @@ class GridContext:
         e, a = C.c_int(0), C.c_int(0)
         call("pp2_model_dict_info", self._h, C.byref(e), C.byref(a))
         return e.value, bool(a.value)
+
+    # ------------------------------------------------------------ live updates
+    def map_update(self, patch, x0: int = 0, y0: int = 0):
+        """Rows [y0, y0 + h) x columns [x0, x0 + w) of the map take ``patch``
+        ((h, w) uint8, 1 = occupied); under a generated model the changed
+        cells are regenerated in place (pp2_map_update).  State is kept: the
+        caller re-solves (``mdp_resolve``)."""
+        patch = np.ascontiguousarray(patch, dtype=np.uint8)
+        if patch.ndim != 2:
+            raise ValueError("patch must be 2-D (h, w)")
+        call("pp2_map_update", self._h, int(x0), int(y0), patch.shape[1],
+             patch.shape[0], _u8(patch))
+
+    def goal_set(self, goal):
+        """Move the goal (pp2_goal_set); ``self.goal`` follows."""
+        gx, gy = int(goal[0]), int(goal[1])
+        call("pp2_goal_set", self._h, gx, gy)
+        self.goal = (gx, gy)
+
+    def map_get(self):
+        """(map (H, W) uint8, goal (gx, gy)) in force (pp2_map_get)."""
+        m = np.empty((self.global_height, self.width), np.uint8)
+        gx, gy = C.c_int32(), C.c_int32()
+        call("pp2_map_get", self._h, _u8(m), C.byref(gx), C.byref(gy))
+        return m, (gx.value, gy.value)
+
+    def map_update_info(self):
+        """(updates that changed the model, served by the patch path, served
+        by the full build, dictionary rows the last one appended)."""
+        u, i, r = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        a = C.c_int()
+        call("pp2_map_update_info", self._h, C.byref(u), C.byref(i), C.byref(r),
+             C.byref(a))
+        return u.value, i.value, r.value, a.value
 
     def resident_launches(self):
         """(tile-resident loop launches, resident MDP-solve launches) so far."""
@@ -233,6 +268,13 @@ class GridContext:
         s = C.c_int()
         nrm = C.c_double()
         call("pp2_mdp_solve", self._h, int(max_sweeps), C.byref(s), C.byref(nrm))
+        return s.value, nrm.value
+
+    def mdp_resolve(self, max_sweeps: int = 0):
+        """``mdp_solve`` from the current J instead of J = 0 (pp2_mdp_resolve)."""
+        s = C.c_int()
+        nrm = C.c_double()
+        call("pp2_mdp_resolve", self._h, int(max_sweeps), C.byref(s), C.byref(nrm))
         return s.value, nrm.value
 
     def mdp_get(self):

@@ -19,6 +19,7 @@
 // sums use the dense kernels' cell->block mapping and reduction tree, so the
 // coded and dense paths give bit-identical beliefs, masses, values and actions.
 #include "pp2_coded_dev.h"
+#include "pp2_model_dev.h"
 
 namespace pp2 {
 
@@ -37,27 +38,8 @@ namespace {
 constexpr int kQuarter = kBlock;  // a dense-kernel block: 256 threads, 1024 cells
 
 // ---------------------------------------------------------------- build
-__device__ __forceinline__ float tuple_value(const PlaneSet& T, const PlaneSet& C,
-                                             const PlaneSet& R, const PlaneSet& L, int y,
-                                             int x, int k) {
-  if (k < 90) {
-    const int u = k / 10, i = k % 10;
-    return i < 9 ? T.p[(long long)y * T.rs + (long long)(9 * u + i) * T.ps + x]
-                 : C.p[(long long)y * C.rs + (long long)u * C.ps + x];
-  }
-  if (k < kDictTuple) return L.p[(long long)y * L.rs + (long long)(k - 90) * L.ps + x];
-  return 0.0f;
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t h) {
-  h ^= h >> 31;
-  h *= 0x7fb5d329728ea185ull;
-  h ^= h >> 27;
-  h *= 0x81dadef4bc2dd44dull;
-  h ^= h >> 33;
-  return h;
-}
-
+// (tuple_value, tuple_hash, tuple_differs: pp2_model_dev.h, shared with the
+// map patch)
 // hash of the kDictTuple-value tuple of every cell in rows [-1, rows]
 __global__ __launch_bounds__(kBlock) void k_dict_hash(Geom g, PlaneSet T, PlaneSet C,
                                                       PlaneSet R, PlaneSet L,
@@ -66,12 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_dict_hash(Geom g, PlaneSet T, PlaneS
   const long long n = (long long)(g.rows + 2 * g.halo) * g.wp;
   if (i >= n) return;
   const int y = (int)(i / g.wp) - g.halo, x = (int)(i % g.wp);
-  uint64_t h = 0x9e3779b97f4a7c15ull;
-  for (int k = 0; k < kDictTuple; ++k) {
-    const uint32_t w = __float_as_uint(tuple_value(T, C, R, L, y, x, k));
-    h = mix64(h ^ (w + 0x632be59bd9b4e019ull * (uint64_t)(k + 1)));
-  }
-  out[i] = h;
+  out[i] = tuple_hash(T, C, R, L, y, x);
 }
 
 __global__ __launch_bounds__(kBlock) void k_dict_gather(Geom g, PlaneSet T, PlaneSet C,
@@ -95,10 +72,7 @@ __global__ __launch_bounds__(kBlock) void k_dict_verify(Geom g, PlaneSet T, Plan
   const long long n = (long long)(g.rows + 2 * g.halo) * g.wp;
   if (i >= n) return;
   const int y = (int)(i / g.wp) - g.halo, x = (int)(i % g.wp);
-  const float* d = dict + (long long)code[i] * kDictRow;
-  int diff = 0;
-  for (int k = 0; k < kDictTuple; ++k)
-    diff |= __float_as_uint(tuple_value(T, C, R, L, y, x, k)) != __float_as_uint(d[k]);
+  const int diff = tuple_differs(T, C, R, L, y, x, dict + (long long)code[i] * kDictRow);
   if (diff) atomicOr(bad, 1);
 }
 

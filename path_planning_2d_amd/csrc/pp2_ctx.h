@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "pp2.h"
@@ -242,6 +243,25 @@ struct pp2_ctx {
   int group_size = 0;                // shards in the group
 
   pp2rt::PbviState* pbvi = nullptr;  // PBVI belief set / alpha vectors (pp2_pbvi.cpp)
+
+  // Live map and goal updates (pp2_map_update, pp2_goal_set).
+  // Host mirrors kept from the dictionary build: the hash -> entry map, the
+  // dictionary rows and the code plane (all rows, as code_alloc + kGuard), and
+  // their device table (uploaded by the first update after a build).
+  std::vector<uint8_t> h_map;      // the map in force (unsharded contexts; else empty)
+  bool model_generated = false;    // the model in force: pp2_model_generate's, kept so by updates
+  unsigned model_serial = 0;       // advanced by every update that changes the model
+  int map_incremental = 1;         // PP2_TUNE_MAP_INCREMENTAL
+  long long map_updates = 0, map_patched = 0, map_rebuilds = 0;  // pp2_map_update_info
+  int map_added = 0;               // dictionary rows the last update appended
+  std::unordered_map<uint64_t, int> dict_ids;
+  std::vector<float> h_dict;
+  std::vector<uint16_t> h_code;
+  unsigned long long* d_tab_keys = nullptr;  // kPatchTab keys (0: empty slot)
+  int* d_tab_vals = nullptr;                 // ... and their entries
+  int* d_patch_out = nullptr;                // {bad, misses}
+  pp2::PatchMiss* d_miss = nullptr;          // kPatchMissCap records
+  bool patch_tab_ok = false;                 // the device table matches dict_ids
 };
 
 namespace pp2rt {
@@ -278,6 +298,8 @@ int loop_launch(pp2_ctx* c, int e, uint8_t u, uint8_t z, const float* in_partial
                 const float* in_sum, float* in_sum_out, int* nparts, float scale = 1.0f);
 int mdp_sweep_once(pp2_ctx* c);
 int build_model_dict(pp2_ctx* c);
+// model-caching objects (the planner) refuse to run once this has moved on
+inline unsigned model_serial(const pp2_ctx* c) { return c->model_serial; }
 bool coded_active(const pp2_ctx* c);
 // Step pairs (k_loop_pair_coded) on this context: sparse coded model, a
 // block depth >= 2, a fitting geometry and (unless PP2_TUNE_STEP_PAIRS = 2

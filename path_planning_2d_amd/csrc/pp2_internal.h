@@ -204,6 +204,30 @@ hipError_t launch_dict_gather(hipStream_t st, const Geom& g, PlaneSet T, PlaneSe
                               PlaneSet L, const int* reps, int entries, float* dict);
 hipError_t launch_dict_verify(hipStream_t st, const Geom& g, PlaneSet T, PlaneSet C, PlaneSet R,
                               PlaneSet L, const uint16_t* code_all, const float* dict, int* bad);
+// Map patch (pp2_map_patch.hip): the model of the cells of two rectangles of
+// the grid proper (local rows and columns; w or h of 0: none) regenerated
+// from the map and re-coded through the table hash -> entry (kPatchTab slots,
+// key 0 empty, linear probing; null: planes only).  out = {bad, misses}; the
+// first miss_cap misses are listed.  code = code plane at (row 0, x 0).
+struct PatchRect {
+  int x0, y0, w, h;
+};
+struct PatchMiss {
+  unsigned long long hash;
+  int cell;  // y * wp + x
+  int code;  // the host's answer (launch_patch_assign)
+};
+constexpr int kPatchTab = 2048;  // > 2 * kDictMax, a power of two
+static_assert(kPatchTab > 2 * kDictMax && (kPatchTab & (kPatchTab - 1)) == 0, "patch table size");
+hipError_t launch_model_patch(hipStream_t st, const Geom& g, const uint8_t* map, int gx, int gy,
+                              PlaneSet T, PlaneSet L, PlaneSet R, PlaneSet C, PatchRect r0,
+                              PatchRect r1, uint16_t* code, const float* dict,
+                              const unsigned long long* tab_keys, const int* tab_vals, int* out,
+                              PatchMiss* miss, int miss_cap);
+// the first n misses take their codes (< entries), each verified against its row
+hipError_t launch_patch_assign(hipStream_t st, const Geom& g, PlaneSet T, PlaneSet C, PlaneSet R,
+                               PlaneSet L, const PatchMiss* miss, int n, int entries,
+                               uint16_t* code, const float* dict, int* out);
 // code = code plane at (row 0, x 0); rows = LDS-layout dictionary rows (E x
 // factored if sparse else E x kDictTC, T entries pre-multiplied by gamma); lz =
 // the L_z column (E floats); tu = raw T of action u per entry (E x 4 sparse,

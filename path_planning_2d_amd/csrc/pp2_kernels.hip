@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "pp2_device.h"
+#include "pp2_model_dev.h"
 
 namespace pp2 {
 
@@ -26,29 +27,10 @@ int cells_grid(const Geom& g, int cpt) {
 }
 
 // ============================================================================
-// (a1) model generation -- cudaGenerateModelData, POMDP
-// (src/pomdp/model_generation_cuda.cu:161-347) and MDP
-// (src/mdp/path_planning_2d_cuda.cu:76-213).  T is identical for both models,
-// so one T serves the Bellman sweep and the belief update; R is the POMDP
-// stage reward, C the MDP stage cost.  Pad cells and rows outside the global
-// grid are written as zeros.
+// (a1) model generation: one thread per cell of rows [-halo, rows + halo),
+// the cell's model by pp2_model_dev.h's model_cell (shared with the map patch,
+// pp2_map_patch.hip).
 // ============================================================================
-__device__ __forceinline__ void base_kernel(int u, float tp[9]) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) tp[i] = 0.0f;
-  switch (u) {
-    case 0: tp[0] = 0.7f; tp[1] = 0.1f; tp[3] = 0.1f; tp[4] = 0.1f; break;
-    case 1: tp[0] = 0.1f; tp[1] = 0.7f; tp[2] = 0.1f; tp[4] = 0.1f; break;
-    case 2: tp[1] = 0.1f; tp[2] = 0.7f; tp[4] = 0.1f; tp[5] = 0.1f; break;
-    case 3: tp[0] = 0.1f; tp[3] = 0.7f; tp[4] = 0.1f; tp[6] = 0.1f; break;
-    case 4: tp[4] = 1.0f; break;
-    case 5: tp[2] = 0.1f; tp[4] = 0.1f; tp[5] = 0.7f; tp[8] = 0.1f; break;
-    case 6: tp[3] = 0.1f; tp[4] = 0.1f; tp[6] = 0.7f; tp[7] = 0.1f; break;
-    case 7: tp[4] = 0.1f; tp[6] = 0.1f; tp[7] = 0.7f; tp[8] = 0.1f; break;
-    default: tp[4] = 0.1f; tp[5] = 0.1f; tp[7] = 0.1f; tp[8] = 0.7f; break;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void k_model_gen(
     Geom g, const uint8_t* __restrict__ map, int gx, int gy, PlaneSet T,
     PlaneSet L, PlaneSet R, PlaneSet C) {
@@ -56,68 +38,7 @@ __global__ __launch_bounds__(kBlock) void k_model_gen(
   const int x = (int)(t % g.wp);
   const int y = (int)(t / g.wp) - g.halo;  // local row in [-halo, rows + halo)
   if (y >= g.rows + g.halo) return;
-  const int ry = g.row0 + y;          // global row
-  const bool valid = x < g.width && ry >= 0 && ry < g.grows;
-
-  uint8_t lm[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int nx = x + i % 3 - 1, ny = ry + i / 3 - 1;
-    lm[i] = (!valid || nx < 0 || nx >= g.width || ny < 0 || ny >= g.grows)
-                ? 1 : map[(long long)ny * g.width + nx];
-  }
-  const bool at_goal = (unsigned)x == (unsigned)gx && (unsigned)ry == (unsigned)gy;
-  float mr[9], mc[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    mr[i] = lm[i] == 1 ? -2.0f : -1.0f;
-    mc[i] = lm[i] == 1 ? 2.0f : 1.0f;
-  }
-  for (int u = 0; u < 9; ++u) {
-    float tp[9], nv[9];
-    base_kernel(u, tp);
-    // POMDP naive = base kernel (copied before the shift, :213-214)
-#pragma unroll
-    for (int i = 0; i < 9; ++i) nv[i] = tp[i];
-    // MDP naive = base kernel after the trap override (:131-137)
-    float nm[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) nm[i] = (lm[4] == 1) ? (i == 4 ? 1.0f : 0.0f) : tp[i];
-    // occupied neighbour -> mass stays (:219-224), in index order
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-      if (lm[i] == 1 && i != 4) { tp[4] += tp[i]; tp[i] = 0.0f; }
-    if (lm[4] == 1) {  // trapped (:230-233)
-#pragma unroll
-      for (int i = 0; i < 9; ++i) tp[i] = 0.0f;
-      tp[4] = 1.0f;
-    }
-    float r = 0.0f, c = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      r = __builtin_fmaf(mr[i], nv[i], r);  // cudaStageReward :288-291
-      c = __builtin_fmaf(mc[i], nm[i], c);  // cudaStageCost   :166-169
-    }
-    if (u == 4) {
-      r = at_goal ? 0.0f : -2.0f;  // :293
-      c = at_goal ? 0.0f : 2.0f;   // mdp :171
-    }
-    const long long rowT = (long long)y * T.rs + x;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) T.p[rowT + (9 * u + i) * T.ps] = valid ? tp[i] : 0.0f;
-    R.p[(long long)y * R.rs + u * R.ps + x] = valid ? r : 0.0f;
-    C.p[(long long)y * C.rs + u * C.ps + x] = valid ? c : 0.0f;
-  }
-  // cudaMeasurementLikelihood (:238-264): m = {up, left, right, down}
-  const uint8_t m0 = lm[1], m1 = lm[3], m2 = lm[5], m3 = lm[7];
-  for (int i = 0; i < 16; ++i) {
-    const float l0 = (((i >> 0) & 1) == m0) ? (float)0.98 : (float)0.02;
-    const float l1 = (((i >> 1) & 1) == m1) ? (float)0.98 : (float)0.02;
-    const float l2 = (((i >> 2) & 1) == m2) ? (float)0.98 : (float)0.02;
-    const float l3 = (((i >> 3) & 1) == m3) ? (float)0.98 : (float)0.02;
-    const float l = ((l0 * l1) * l2) * l3;
-    L.p[(long long)y * L.rs + i * L.ps + x] = valid ? l : 0.0f;
-  }
+  model_cell(g, map, gx, gy, T, L, R, C, x, y);
 }
 
 hipError_t launch_model_gen(hipStream_t st, const Geom& g, const uint8_t* map,

@@ -49,18 +49,23 @@ inline uint32_t bits(float v) {
 }
 }  // namespace masked_detail
 
-// code: the code plane at (row -1, x 0), rows + 2 rows of wp codes (< E);
-// dict: E rows of dict_row floats, [a][T_a0 .. T_a8, C_a] at 10 * a.
-inline MaskedModel masked_admit(const uint16_t* code, int wp, int rows, const float* dict, int E,
-                                int dict_row, float gamma) {
-  using namespace masked_detail;
-  MaskedModel m;
-  if (E <= 0 || wp <= 0 || rows <= 0) return m;
-  m.blocked.assign((size_t)E, 0);
-  // per entry: F; else the neighbours (bit i, T index i) that must be blocked
-  std::vector<uint16_t> need((size_t)E, 0);
-  bool have_main = false, have_side = false;
+namespace masked_detail {
+// The per-entry half of the admission: F per entry, else the neighbours
+// (bit i, T index i) that must be blocked, and the two weights.
+struct MaskedEntries {
+  bool ok = false;
+  std::vector<uint8_t> blocked;
+  std::vector<uint16_t> need;
   uint32_t wm = 0u, ws = 0u;
+};
+
+inline MaskedEntries masked_entries(const float* dict, int E, int dict_row, float gamma) {
+  MaskedEntries m;
+  m.blocked.assign((size_t)E, 0);
+  m.need.assign((size_t)E, 0);
+  bool have_main = false, have_side = false;
+  uint32_t& wm = m.wm;
+  uint32_t& ws = m.ws;
   for (int e = 0; e < E; ++e) {
     const float* d = dict + (size_t)e * dict_row;
     bool all_zero = true, same = true;
@@ -103,20 +108,29 @@ inline MaskedModel masked_admit(const uint16_t* code, int wp, int rows, const fl
     uint16_t nb = 0;
     for (int i = 0; i < 9; ++i)
       if (i != 4 && state[i] == 1) nb |= (uint16_t)(1u << i);
-    need[e] = nb;
+    m.need[e] = nb;
   }
-  // The relation, cell by cell: F of the 8 neighbours against the entry's need,
-  // in two passes without a data-dependent branch -- h = F(x - 1) | F(x) << 1 |
-  // F(x + 1) << 2 per cell (a row of 7s above and below the plane), then the
-  // three rows' triples against the need (a blocked cell compares nothing).
-  const int R = rows + 2;
-  std::vector<uint8_t> h((size_t)(R + 2) * wp, 7);
+  m.ok = true;
+  return m;
+}
+
+// The relation, cell by cell, over rows [r_lo, r_hi) of a plane of R rows of
+// wp codes: F of the 8 neighbours against the entry's need, in two passes
+// without a data-dependent branch -- h = F(x - 1) | F(x) << 1 | F(x + 1) << 2
+// per cell of rows [r_lo - 1, r_hi] (the plane's own rows where it has them, a
+// row of 7s above and below the plane), then the three rows' triples against
+// the need (a blocked cell compares nothing).
+inline bool masked_cells(const uint16_t* code, int wp, int R, int E, const uint8_t* bl,
+                         const uint16_t* nd, int r_lo, int r_hi) {
+  if (r_lo < 0) r_lo = 0;
+  if (r_hi > R) r_hi = R;
+  if (r_lo >= r_hi) return true;
+  const int nr = r_hi - r_lo;
+  std::vector<uint8_t> h((size_t)(nr + 2) * wp, 7);  // h row j: plane row r_lo - 1 + j
   unsigned bad = 0;
-  const uint8_t* const bl = m.blocked.data();
-  const uint16_t* const nd = need.data();
-  for (int r = 0; r < R; ++r) {
+  for (int r = r_lo > 0 ? r_lo - 1 : 0; r < (r_hi < R ? r_hi + 1 : R); ++r) {
     const uint16_t* cr = code + (size_t)r * wp;
-    uint8_t* __restrict hr = &h[(size_t)(r + 1) * wp];
+    uint8_t* __restrict hr = &h[(size_t)(r - r_lo + 1) * wp];
     unsigned prev = 1, cur = cr[0] < E ? bl[cr[0]] : 1;
     bad |= cr[0] >= E;
     for (int x = 0; x < wp; ++x) {
@@ -131,10 +145,10 @@ inline MaskedModel masked_admit(const uint16_t* code, int wp, int rows, const fl
       cur = next;
     }
   }
-  if (bad) return m;
-  for (int r = 0; r < R; ++r) {
+  if (bad) return false;
+  for (int r = r_lo; r < r_hi; ++r) {
     const uint16_t* cr = code + (size_t)r * wp;
-    const uint8_t* h0 = &h[(size_t)r * wp];
+    const uint8_t* h0 = &h[(size_t)(r - r_lo) * wp];
     const uint8_t* h1 = h0 + wp;
     const uint8_t* h2 = h1 + wp;
     for (int x = 0; x < wp; ++x) {
@@ -143,11 +157,41 @@ inline MaskedModel masked_admit(const uint16_t* code, int wp, int rows, const fl
       bad |= (nb ^ nd[cr[x]]) & (own - 1u);
     }
   }
-  if (bad) return m;
-  std::memcpy(&m.w_main, &wm, 4);
-  std::memcpy(&m.w_side, &ws, 4);
+  return !bad;
+}
+}  // namespace masked_detail
+
+// code: the code plane at (row -1, x 0), rows + 2 rows of wp codes (< E);
+// dict: E rows of dict_row floats, [a][T_a0 .. T_a8, C_a] at 10 * a.
+inline MaskedModel masked_admit(const uint16_t* code, int wp, int rows, const float* dict, int E,
+                                int dict_row, float gamma) {
+  using namespace masked_detail;
+  MaskedModel m;
+  if (E <= 0 || wp <= 0 || rows <= 0) return m;
+  MaskedEntries en = masked_entries(dict, E, dict_row, gamma);
+  m.blocked.swap(en.blocked);
+  if (!en.ok) return m;
+  if (!masked_cells(code, wp, rows + 2, E, m.blocked.data(), en.need.data(), 0, rows + 2))
+    return m;
+  std::memcpy(&m.w_main, &en.wm, 4);
+  std::memcpy(&m.w_side, &en.ws, 4);
   m.ok = true;
   return m;
+}
+
+// The windowed form, for a plane that masked_admit admitted before codes of
+// its rows [r_lo + 1, r_hi - 1) changed (r_lo, r_hi: rows of the plane, row 0
+// being the grid's row -1; clipped to it): the entries' half as above, the
+// cells' relation over rows [r_lo, r_hi) alone, read against their true
+// neighbour rows r_lo - 1 and r_hi.  True iff masked_admit would still admit
+// the plane, given that every row outside the window still satisfies it.
+inline bool masked_admit_window(const uint16_t* code, int wp, int rows, const float* dict, int E,
+                                int dict_row, float gamma, int r_lo, int r_hi) {
+  using namespace masked_detail;
+  if (E <= 0 || wp <= 0 || rows <= 0) return false;
+  const MaskedEntries en = masked_entries(dict, E, dict_row, gamma);
+  if (!en.ok) return false;
+  return masked_cells(code, wp, rows + 2, E, en.blocked.data(), en.need.data(), r_lo, r_hi);
 }
 
 }  // namespace pp2

@@ -283,6 +283,8 @@ int create_impl(pp2_ctx** out, int device, uint32_t grows, uint32_t width,
   if (hipMemcpyAsync(c->d_map_alloc, map + mlo * (long long)width, map_bytes,
                      hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return fail(set_err(PP2_EHIP, "map upload"));
+  // (an unsharded context keeps the whole map: pp2_map_update / pp2_map_get)
+  if (!shard) c->h_map.assign(map, map + (size_t)grows * width);
 
   int s = PP2_OK;
   const int dh = c->dense_halo;
@@ -438,6 +440,7 @@ using pp2::finite_nonneg;
 int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Planes* mR,
                      const Planes* mC);
 int build_model_dict(pp2_ctx* c) { return build_model_dict(c, &c->T, &c->L, &c->R, &c->C); }
+static int derive_dict_tables(pp2_ctx* c, int E);
 
 // (mT .. mC: the dense model over rows [-g.halo, rows + g.halo) -- the
 // context's planes, or pp2_model_generate's transient full-halo copy)
@@ -452,6 +455,11 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
   ++c->agree_gen;      // ... and agreed again (pp2_loop_run)
   const long long n = (long long)(c->g.rows + 2 * c->g.halo) * c->g.wp;
   break_pipeline(c);
+  // the host mirrors the map patch works from (pp2_map_update): rebuilt below
+  c->dict_ids.clear();
+  c->h_dict.clear();
+  c->h_code.clear();
+  c->patch_tab_ok = false;
   if (!c->code_alloc) {
     if (hipMalloc(&c->code_alloc, (size_t)(n + 2 * kGuard) * sizeof(uint16_t)) != hipSuccess ||
         hipMalloc(&c->d_dict, (size_t)pp2::kDictMax * pp2::kDictRow * sizeof(float)) != hipSuccess ||
@@ -520,6 +528,24 @@ int build_model_dict(pp2_ctx* c, const Planes* mT, const Planes* mL, const Plane
                         c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (bad) return PP2_OK;
+  c->dict_ids.swap(ids);
+  c->h_dict.swap(dh);
+  c->h_code.swap(code);
+  const int s = derive_dict_tables(c, E);
+  if (c->h_map.empty()) {  // a row shard takes no map update: no mirrors to keep
+    std::unordered_map<uint64_t, int>().swap(c->dict_ids);
+    std::vector<float>().swap(c->h_dict);
+    std::vector<uint16_t>().swap(c->h_code);
+  }
+  return s;
+}
+
+// The tables derived from the dictionary rows (c->h_dict, E of them) and the
+// code plane (c->h_code): the second half of build_model_dict, and of a map
+// patch that appended rows (pp2_map_update).  Sets dict_n = E.
+int derive_dict_tables(pp2_ctx* c, int E) {
+  const std::vector<float>& dh = c->h_dict;
+  const std::vector<uint16_t>& code = c->h_code;
   // The scalar properties and the path gates: pp2_dict_props.h.  LDS-layout
   // rows: sparse (factored) when every T entry off the base-kernel support is
   // +0.0 and the model keeps J finite and >= +0 (always so for generated
@@ -1757,6 +1783,9 @@ int pp2_destroy(pp2_ctx* c) {
   if (c->d_vec) (void)hipFree(c->d_vec);
   for (float* p : {c->d_dict, c->d_rows, c->d_dl, c->d_tu, c->d_rfact})
     if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->d_tab_keys, (void*)c->d_tab_vals, (void*)c->d_miss,
+                  (void*)c->d_patch_out})
+    if (p) (void)hipFree(p);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return PP2_OK;
@@ -1852,6 +1881,11 @@ int pp2_set_tuning(pp2_ctx* c, int key, int value) {
       c->comm_dropped = 0;
       c->comm_open = false;
       return PP2_OK;
+    case PP2_TUNE_MAP_INCREMENTAL:
+      if (value < 0 || value > 1)
+        return set_err(PP2_EINVAL, "map incremental %d not in [0, 1]", value);
+      c->map_incremental = value;
+      return PP2_OK;
     case PP2_TUNE_HALO_DEPTH:
       if (value < 1 || value > c->kdepth_max)
         return set_err(PP2_EINVAL, "halo depth %d not in [1, %d]", value, c->kdepth_max);
@@ -1887,6 +1921,7 @@ int pp2_model_generate(pp2_ctx* c) {
     HIPCHK(pp2::launch_model_gen(c->stream, c->g, c->d_map, c->gx, c->gy, c->T.v,
                                  c->L.v, c->R.v, c->C.v));
     c->model_ready = true;
+    c->model_generated = true;
     const int s = build_model_dict(c);
     if (s == PP2_OK) generated_model_flags(c);
     return s;
@@ -1948,6 +1983,7 @@ int pp2_model_upload(pp2_ctx* c, const float* T, const float* L, const float* R,
   if (R) CHECK(upload_planes(c, c->R, R));
   if (C) CHECK(upload_planes(c, c->C, C));
   c->model_ready = true;
+  c->model_generated = false;  // (pp2_map_update / pp2_goal_set refuse a foreign model)
   // Without a dictionary (too many distinct cells) the model's conditions
   // (pp2_dict_props.h) come from the planes given here, and from the previous
   // model for the others.
@@ -2009,6 +2045,281 @@ int pp2_model_load(pp2_ctx* c, const char* dir) {
   // The MDP cost is not part of the POMDP files; keep/derive it on device.
   if (!c->model_ready) CHECK(pp2_model_generate(c));
   return pp2_model_upload(c, T.data(), L.data(), R.data(), nullptr);
+}
+
+// ---------------------------------------------------------------- live updates
+// pp2_map_update / pp2_goal_set: the stored map or goal is
+// rewritten; under a generated model the cells whose 3x3 occupancy or at_goal
+// changed are regenerated by k_model_patch (pp2_map_patch.hip) and re-coded
+// against the dictionary in force.  Whatever the patch path cannot settle --
+// a hash collision, more misses than the list holds, more than kDictMax rows,
+// tables that stale rows pushed off the sparse form -- goes to the full
+// build_model_dict, which decides as on a fresh context.
+namespace {
+
+constexpr int kPatchMissCap = 1 << 16;
+
+int updatable(pp2_ctx* c, const char* fn) {
+  if (c->comm || c->group || c->nranks > 1 || c->g.rows != c->g.grows || c->g.halo != 1 ||
+      c->h_map.empty())
+    return set_err(PP2_ESTATE, "%s: map and goal updates need an unsharded context (pp2_create), "
+                   "not a row shard, an RCCL rank or a shard-group member", fn);
+  if (c->model_ready && !c->model_generated)
+    return set_err(PP2_ESTATE, "%s: the model in force was uploaded or loaded; regenerating "
+                   "part of it would mix two models (pp2_model_generate first)", fn);
+  return PP2_OK;
+}
+
+// the patch kernel's buffers, and the device table hash -> entry of dict_ids
+int patch_buffers(pp2_ctx* c) {
+  if (!c->d_patch_out) {
+    if (hipMalloc(&c->d_tab_keys, (size_t)pp2::kPatchTab * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&c->d_tab_vals, (size_t)(pp2::kPatchTab + pp2::kDictMax) * sizeof(int)) != hipSuccess ||
+        hipMalloc(&c->d_miss, (size_t)kPatchMissCap * sizeof(pp2::PatchMiss)) != hipSuccess ||
+        hipMalloc(&c->d_patch_out, 2 * sizeof(int)) != hipSuccess) {
+      for (void* p : {(void*)c->d_tab_keys, (void*)c->d_tab_vals, (void*)c->d_miss,
+                      (void*)c->d_patch_out})
+        if (p) (void)hipFree(p);
+      c->d_tab_keys = nullptr;
+      c->d_tab_vals = nullptr;
+      c->d_miss = nullptr;
+      c->d_patch_out = nullptr;
+      return set_err(PP2_ENOMEM, "hipMalloc map patch buffers");
+    }
+    c->patch_tab_ok = false;
+  }
+  if (c->patch_tab_ok) return PP2_OK;
+  std::vector<unsigned long long> keys((size_t)pp2::kPatchTab, 0ull);
+  std::vector<int> vals((size_t)pp2::kPatchTab, -1);
+  for (const auto& kv : c->dict_ids) {
+    if (kv.first == 0ull) continue;  // (0 marks an empty slot: such a tuple always misses)
+    unsigned s = (unsigned)kv.first & (pp2::kPatchTab - 1);
+    while (keys[s] != 0ull) s = (s + 1) & (pp2::kPatchTab - 1);
+    keys[s] = kv.first;
+    vals[s] = kv.second;
+  }
+  HIPCHK(hipMemcpyAsync(c->d_tab_keys, keys.data(), keys.size() * sizeof(unsigned long long),
+                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_tab_vals, vals.data(), vals.size() * sizeof(int),
+                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->patch_tab_ok = true;
+  return PP2_OK;
+}
+
+// The model over the planes as they stand: the full dictionary build, as
+// pp2_model_generate ends.
+int rebuild_dict(pp2_ctx* c) {
+  const int s = build_model_dict(c);
+  if (s == PP2_OK) generated_model_flags(c);
+  return s;
+}
+
+// The model of the cells of r0 and r1 (disjoint, inside the grid, r1 possibly
+// empty) follows the stored map and goal.
+int model_follow(pp2_ctx* c, pp2::PatchRect r0, pp2::PatchRect r1) {
+  ++c->map_updates;
+  c->map_added = 0;
+  ++c->model_serial;   // planners made before this refuse to step
+  c->res_e_dict = -1;  // as build_model_dict: whatever was decided on the old model
+  ++c->agree_gen;
+  break_pipeline(c);
+  if (!c->map_incremental) {
+    ++c->map_rebuilds;
+    HIPCHK(pp2::launch_model_gen(c->stream, c->g, c->d_map, c->gx, c->gy, c->T.v, c->L.v, c->R.v,
+                                 c->C.v));
+    return rebuild_dict(c);
+  }
+  const int wp = c->g.wp, halo = c->g.halo;
+  const size_t nplane = (size_t)(c->g.rows + 2 * halo) * wp;
+  const bool dict = c->dict_n > 0 && c->h_code.size() == nplane && !c->dict_ids.empty() &&
+                    c->h_dict.size() == (size_t)c->dict_n * pp2::kDictRow;
+  if (!dict) {
+    // no dictionary to patch (the last build found too many tuples, or a
+    // collision): the planes alone, then the build a fresh context would run
+    HIPCHK(pp2::launch_model_patch(c->stream, c->g, c->d_map, c->gx, c->gy, c->T.v, c->L.v,
+                                   c->R.v, c->C.v, r0, r1, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, 0));
+    ++c->map_rebuilds;
+    return rebuild_dict(c);
+  }
+  CHECK(patch_buffers(c));
+  HIPCHK(hipMemsetAsync(c->d_patch_out, 0, 2 * sizeof(int), c->stream));
+  HIPCHK(pp2::launch_model_patch(c->stream, c->g, c->d_map, c->gx, c->gy, c->T.v, c->L.v, c->R.v,
+                                 c->C.v, r0, r1, c->d_code, c->d_dict, c->d_tab_keys,
+                                 c->d_tab_vals, c->d_patch_out, c->d_miss, kPatchMissCap));
+  // {bad, misses} and the rectangles' codes into the host mirror (a missed
+  // cell still holds its old code: set below)
+  int out[2] = {1, 0};
+  HIPCHK(hipMemcpyAsync(out, c->d_patch_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+  uint16_t* hc = c->h_code.data() + (size_t)halo * wp;  // the mirror at (row 0, x 0)
+  for (const pp2::PatchRect& r : {r0, r1})
+    if (r.w > 0 && r.h > 0)
+      HIPCHK(hipMemcpy2DAsync(hc + (size_t)r.y0 * wp + r.x0, (size_t)wp * sizeof(uint16_t),
+                              c->d_code + (size_t)r.y0 * wp + r.x0, (size_t)wp * sizeof(uint16_t),
+                              (size_t)r.w * sizeof(uint16_t), (size_t)r.h, hipMemcpyDeviceToHost,
+                              c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  auto full = [&]() {
+    ++c->map_rebuilds;
+    c->map_added = 0;
+    return rebuild_dict(c);
+  };
+  if (out[0] != 0 || out[1] < 0 || out[1] > kPatchMissCap) return full();
+  const int E = c->dict_n;
+  int En = E;
+  if (out[1] > 0) {
+    // new tuples: numbered from E upward in cell order, one row each
+    const int nm = out[1];
+    std::vector<pp2::PatchMiss> miss((size_t)nm);
+    HIPCHK(hipMemcpyAsync(miss.data(), c->d_miss, miss.size() * sizeof(pp2::PatchMiss),
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::sort(miss.begin(), miss.end(),
+              [](const pp2::PatchMiss& a, const pp2::PatchMiss& b) { return a.cell < b.cell; });
+    std::vector<int> reps;
+    for (pp2::PatchMiss& m : miss) {
+      if (m.hash == 0ull || m.cell < 0 || m.cell >= c->g.rows * wp) return full();
+      auto it = c->dict_ids.find(m.hash);
+      if (it == c->dict_ids.end()) {
+        if (En >= pp2::kDictMax) return full();
+        it = c->dict_ids.emplace(m.hash, En++).first;
+        reps.push_back(m.cell + halo * wp);  // (k_dict_gather counts cells from row -halo)
+      }
+      m.code = it->second;
+    }
+    c->patch_tab_ok = false;
+    int* d_reps = c->d_tab_vals + pp2::kPatchTab;
+    HIPCHK(hipMemsetAsync(c->d_patch_out, 0, 2 * sizeof(int), c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_miss, miss.data(), miss.size() * sizeof(pp2::PatchMiss),
+                          hipMemcpyHostToDevice, c->stream));
+    if (En > E) {
+      HIPCHK(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int), hipMemcpyHostToDevice,
+                            c->stream));
+      HIPCHK(pp2::launch_dict_gather(c->stream, c->g, c->T.v, c->C.v, c->R.v, c->L.v, d_reps,
+                                     En - E, c->d_dict + (size_t)E * pp2::kDictRow));
+    }
+    HIPCHK(pp2::launch_patch_assign(c->stream, c->g, c->T.v, c->C.v, c->R.v, c->L.v, c->d_miss, nm,
+                                    En, c->d_code, c->d_dict, c->d_patch_out));
+    c->h_dict.resize((size_t)En * pp2::kDictRow);
+    out[0] = 1;
+    HIPCHK(hipMemcpyAsync(out, c->d_patch_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    if (En > E)
+      HIPCHK(hipMemcpyAsync(c->h_dict.data() + (size_t)E * pp2::kDictRow,
+                            c->d_dict + (size_t)E * pp2::kDictRow,
+                            (size_t)(En - E) * pp2::kDictRow * sizeof(float), hipMemcpyDeviceToHost,
+                            c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out[0] != 0) return full();
+    for (const pp2::PatchMiss& m : miss) hc[m.cell] = (uint16_t)m.code;
+  }
+  if (En > E) {
+    // the derived tables over all rows, stale ones included; a fresh build
+    // may do better where those cost the sparse form or the class tables
+    CHECK(derive_dict_tables(c, En));
+    if (!c->dict_sparse || !c->dict_rfact) return full();
+    c->map_added = En - E;
+  } else if (c->dict_masked) {
+    // every table stands; the masked admission is a relation between a cell
+    // and its 8 neighbours, so only the rows around the change can break it
+    bool ok = true;
+    for (const pp2::PatchRect& r : {r0, r1})
+      if (r.w > 0 && r.h > 0)
+        ok = ok && pp2::masked_admit_window(c->h_code.data() + (size_t)(halo - 1) * wp, wp,
+                                            c->g.rows, c->h_dict.data(), E, pp2::kDictRow,
+                                            c->gamma, r.y0, r.y0 + r.h + 2);
+    if (!ok) CHECK(derive_dict_tables(c, E));
+  } else if (c->dict_rfact && pp2::gate_masked_precheck(c->dict_props, true)) {
+    CHECK(derive_dict_tables(c, E));  // not admitted before: the whole plane decides
+  }
+  ++c->map_patched;
+  return PP2_OK;
+}
+
+}  // namespace
+
+int pp2_map_update(pp2_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                   const uint8_t* patch) {
+  CHECK(check_ctx(c));
+  CHECK(updatable(c, "pp2_map_update"));
+  const uint32_t W = (uint32_t)c->g.width, H = (uint32_t)c->g.rows;
+  if (!patch) return set_err(PP2_EINVAL, "patch is null");
+  if (w == 0 || h == 0 || x0 >= W || y0 >= H || w > W - x0 || h > H - y0)
+    return set_err(PP2_EINVAL, "rectangle %ux%u at (%u, %u) is empty or outside the %ux%u grid", w,
+                   h, x0, y0, W, H);
+  DeviceGuard dg(c->device);
+  // the stored map; the bounding box of the cells whose occupancy changes
+  bool differs = false;
+  int bx0 = (int)W, bx1 = -1, by0 = (int)H, by1 = -1;
+  for (uint32_t y = 0; y < h; ++y) {
+    uint8_t* dst = &c->h_map[(size_t)(y0 + y) * W + x0];
+    const uint8_t* src = patch + (size_t)y * w;
+    for (uint32_t x = 0; x < w; ++x) {
+      if (dst[x] == src[x]) continue;
+      differs = true;
+      if ((dst[x] == 1) != (src[x] == 1)) {
+        bx0 = std::min(bx0, (int)(x0 + x));
+        bx1 = std::max(bx1, (int)(x0 + x));
+        by0 = std::min(by0, (int)(y0 + y));
+        by1 = std::max(by1, (int)(y0 + y));
+      }
+      dst[x] = src[x];
+    }
+  }
+  if (!differs) return PP2_OK;
+  HIPCHK(hipMemcpy2DAsync(c->d_map + (size_t)y0 * W + x0, W, &c->h_map[(size_t)y0 * W + x0], W, w,
+                          h, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (bx1 < 0 || !c->model_ready) return PP2_OK;
+  // a cell's model reads its 3x3 neighbourhood: the box dilated by one cell
+  pp2::PatchRect r;
+  r.x0 = std::max(bx0 - 1, 0);
+  r.y0 = std::max(by0 - 1, 0);
+  r.w = std::min(bx1 + 1, (int)W - 1) - r.x0 + 1;
+  r.h = std::min(by1 + 1, (int)H - 1) - r.y0 + 1;
+  return model_follow(c, r, pp2::PatchRect{0, 0, 0, 0});
+}
+
+int pp2_goal_set(pp2_ctx* c, int32_t gx, int32_t gy) {
+  CHECK(check_ctx(c));
+  CHECK(updatable(c, "pp2_goal_set"));
+  DeviceGuard dg(c->device);
+  const int32_t ox = c->gx, oy = c->gy;
+  if (ox == gx && oy == gy) return PP2_OK;
+  c->gx = gx;
+  c->gy = gy;
+  if (!c->model_ready) return PP2_OK;
+  auto on_grid = [&](int32_t x, int32_t y) {
+    return x >= 0 && x < c->g.width && y >= 0 && y < c->g.rows;
+  };
+  pp2::PatchRect r[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  int n = 0;
+  if (on_grid(ox, oy)) r[n++] = pp2::PatchRect{ox, oy, 1, 1};
+  if (on_grid(gx, gy)) r[n++] = pp2::PatchRect{gx, gy, 1, 1};
+  if (n == 0) return PP2_OK;  // no goal cell before or after: the model stands
+  return model_follow(c, r[0], r[1]);
+}
+
+int pp2_map_get(pp2_ctx* c, uint8_t* map, int32_t* gx, int32_t* gy) {
+  CHECK(check_ctx(c));
+  if (map) {
+    if (c->h_map.empty())
+      return set_err(PP2_ESTATE, "pp2_map_get: a row shard keeps only its window of the map");
+    std::memcpy(map, c->h_map.data(), c->h_map.size());
+  }
+  if (gx) *gx = c->gx;
+  if (gy) *gy = c->gy;
+  return PP2_OK;
+}
+
+int pp2_map_update_info(pp2_ctx* c, long long* updates, long long* incremental,
+                        long long* rebuilds, int* entries_added) {
+  CHECK(check_ctx(c));
+  if (updates) *updates = c->map_updates;
+  if (incremental) *incremental = c->map_patched;
+  if (rebuilds) *rebuilds = c->map_rebuilds;
+  if (entries_added) *entries_added = c->map_added;
+  return PP2_OK;
 }
 
 // ---------------------------------------------------------------- belief
@@ -2105,10 +2416,19 @@ int pp2_mdp_sweep(pp2_ctx* c, int n) {
   return PP2_OK;
 }
 
-int pp2_mdp_solve(pp2_ctx* c, int max_sweeps, int* sweeps, double* final_norm) {
+// pp2_mdp_solve (warm = false: from J = 0) and pp2_mdp_resolve (warm: from the
+// current J, the convergence snapshot set to it -- what pp2_mdp_reset leaves
+// for J = 0).
+static int mdp_solve_from(pp2_ctx* c, bool warm, int max_sweeps, int* sweeps, double* final_norm) {
   CHECK(check_model(c));
   DeviceGuard dg(c->device);
-  CHECK(pp2_mdp_reset(c));
+  if (warm) {
+    const Planes& J = c->J[c->jcur];
+    HIPCHK(hipMemcpyAsync(c->Jsnap.alloc, J.alloc, J.floats * sizeof(float),
+                          hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    CHECK(pp2_mdp_reset(c));
+  }
   // double max_optimal_cost = 5.0/(1.0-discount_factor) (path_planning_2d.cu:221)
   const double max_cost = 5.0 / (1.0 - (double)c->gamma);
   if (solve_ready(c)) {
@@ -2130,6 +2450,14 @@ int pp2_mdp_solve(pp2_ctx* c, int max_sweeps, int* sweeps, double* final_norm) {
   if (sweeps) *sweeps = total;
   if (final_norm) *final_norm = norm;
   return PP2_OK;
+}
+
+int pp2_mdp_solve(pp2_ctx* c, int max_sweeps, int* sweeps, double* final_norm) {
+  return mdp_solve_from(c, false, max_sweeps, sweeps, final_norm);
+}
+
+int pp2_mdp_resolve(pp2_ctx* c, int max_sweeps, int* sweeps, double* final_norm) {
+  return mdp_solve_from(c, true, max_sweeps, sweeps, final_norm);
 }
 
 int pp2_mdp_get(pp2_ctx* c, float* J, uint8_t* A) {

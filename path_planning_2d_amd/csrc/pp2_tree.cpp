@@ -270,6 +270,8 @@ struct pp2_planner {
   long long t_n = 0;
   std::chrono::steady_clock::time_point t_last_store{};
   unsigned frows_version = 0;   // the context's fib_version d_frows was packed from (0: never)
+  unsigned model_serial = 0;    // the context's model_serial the cached T / L (hT, hL, the
+                                // packed rows) were read at: a map or goal update moves it on
   hipStream_t side = nullptr;   // reward chains beside the child chains
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_kids = nullptr;
   hipEvent_t ev_kept = nullptr;  // the kept children's rows are stored (main -> side)
@@ -1459,6 +1461,7 @@ int pp2_planner_create(pp2_planner** out, pp2_ctx* c, const pp2_planner_params* 
     pp2_planner_destroy(p);
     return s;
   };
+  p->model_serial = pp2rt::model_serial(c);
   p->hT.resize(p->n * 81);
   p->hL.resize(p->n * 16);
   int s = pp2_model_download(c, p->hT.data(), p->hL.data(), nullptr, nullptr);
@@ -1750,6 +1753,9 @@ int pp2_planner_step(pp2_planner* p, uint8_t action, uint8_t observation,
   if (p->timing && p->t_steps > 0)
     p->t_out += std::chrono::duration<double, std::micro>(t_in - p->t_ret_step).count();
   pp2_ctx* c = p->ctx;
+  if (p->model_serial != pp2rt::model_serial(c))
+    return set_err(PP2_ESTATE, "the context's map or goal was updated after this planner was "
+                   "created (it caches the model): create a new planner");
   DeviceGuard dg(c->device);
   if (!p->root) {
     if (!belief) return set_err(PP2_EINVAL, "first plan step needs a belief");
