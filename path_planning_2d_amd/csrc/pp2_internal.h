@@ -434,11 +434,9 @@ inline Geom transposed_geom(const Geom& g) {
   return t;
 }
 // masked: run the masked-support instance (an unsharded whole-row plan of a
-// model admitted by masked_admit, the FX / GC tables in a.rfact) when the
-// library was built with it (resident_masked_built), else null.
+// model admitted by masked_admit, the FX / GC tables in a.rfact), else null.
 hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const ResidentRun& a,
                                 const ResidentMasked* masked = nullptr);
-bool resident_masked_built();
 // Row-shard boundary kernels (pp2_resident.hip).  vec holds one
 // record of kVecRec floats per rank, {owned mass, shift, lost}: the mass of the
 // n partials (k_sum_finalize's tree), (float) *shift (0 if shift is null) and,

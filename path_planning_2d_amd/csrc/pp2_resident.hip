@@ -30,7 +30,7 @@
 //     in the whole-row instance only the steps whose slot is read -- the one
 //     before a block start and the last -- compute partials at all, and the
 //     step before a block start publishes them and arrives right after its
-//     gather, a backup ahead of the step's end (PP2_RES_EARLY);
+//     gather, a backup ahead of the step's end (`early`);
 //   * the last step stores b, J and A for the whole grid (non-temporal) and its
 //     partials to the context's pending buffer -- b and J into the OTHER
 //     ping-pong buffers, so the run's inputs survive it.
@@ -182,10 +182,7 @@ __device__ __forceinline__ int pow2_shift_lagged(float S, int prev) {
 // wave_reduce_partials (pp2_device.h) with sc1 loads: the partials were
 // stored by other CUs inside this launch.  Same association, bit for bit.
 // kRedQ quads per lane in flight per round trip.
-#ifndef PP2_REDQ
-#define PP2_REDQ 8
-#endif
-constexpr int kRedQ = PP2_REDQ;
+constexpr int kRedQ = 8;
 __device__ __forceinline__ float wave_reduce_partials_sc1(const float* p, int n) {
   const Rsrc r = make_rsrc(p);
   const int lane = threadIdx.x & 63;
@@ -244,16 +241,6 @@ constexpr bool belief_row_used(int U, int r) {
 struct ClassRows {
   uint32_t m[3], e[3];
 };
-// The step's serial chain (A/B builds: 0 keeps the earlier form)
-#ifndef PP2_RES_GATHER1
-#define PP2_RES_GATHER1 1  // the whole-row gather's table reads in one LDS round trip
-#endif
-#ifndef PP2_RES_TRAJ_SGPR
-#define PP2_RES_TRAJ_SGPR 1  // (u, z) from a trajectory word held in an SGPR
-#endif
-#ifndef PP2_RES_PHASE_CTR
-#define PP2_RES_PHASE_CTR 1  // the block phase as a counter, not two % depth per step
-#endif
 __device__ __forceinline__ void load_class_rows(const uint8_t* prow, int ps, int x0, ClassRows& c) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -301,7 +288,7 @@ __device__ __forceinline__ void belief_fact(const uint8_t* prow, int ps, int x0,
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) p[k] = 0.0f;
-  if constexpr (PRE && PP2_RES_GATHER1) {
+  if constexpr (PRE) {
     // The whole-row instance: the action's QR values (one per cell and
     // support offset, <= 16 a quad) and the quad's four LT values are all
     // issued before the first fmaf, the order pinned by a scheduling barrier
@@ -357,9 +344,6 @@ __device__ __forceinline__ void belief_fact(const uint8_t* prow, int ps, int x0,
 // the two neighbour bytes lh (x0 - 1 in bits 0-7, x0 + 4 in bits 8-15), so
 // the gather's table reads issue at the step's top, without the class-byte
 // LDS round trip before them.  Slots in (action, row) order.
-#ifndef PP2_RES_HOIST
-#define PP2_RES_HOIST 1  // (A/B builds: 0 keeps the LDS class reads in the TC = 3 instance)
-#endif
 struct ClsSlots {
   int s[9][3];
   int n;
@@ -491,26 +475,21 @@ __device__ __forceinline__ void belief_any_pre(int u, int x0, uint32_t lx4, int 
 }
 
 // The masked-support form of the whole-row instance (models
-// admitted by pp2_masked.h; 0 compiles the instance out and every launch runs
-// the class-table form).  The tile's LDS planes and the published granules
+// admitted by pp2_masked.h).  The tile's LDS planes and the published granules
 // hold b and J with blocked cells stored as +0 (the lane's own unmasked values
 // persist in p / best), so an off-centre weight is the wave-uniform constant
 // of the base kernel and the zero sits in the operand: no class planes, no QR
 // quads, one 8-B {gT centre, C} record per (action, cell) in the backup.
-#ifndef PP2_RES_MASKED
-#define PP2_RES_MASKED 1
-#endif
-// The masked instances' step without most of its non-arithmetic VALU work
-// (profiles/r12; 0 compiles them to the earlier instructions;
-// the other instances are the same either way):
+// The masked instances' step is written without most of the non-arithmetic
+// VALU work of the other instances' (profiles/r12):
 //   * every window row is read from LDS into the same registers, whatever its
 //     source.  The tile buffers are laid out with a row that is never written
 //     in front of each and behind the last (lean_tile_floats), so rows ty - 1
 //     and ty + 1 exist for every wave -- a tile row, or zeros: off the grid, or
 //     a neighbour tile's, whose granules are then OR-ed over the zeros -- and
-//     the six row addresses are one parity offset plus constants.  The earlier
-//     form reads the two rows under wave-uniform branches, so their registers
-//     stay live, undefined, on the paths that take the row from elsewhere and
+//     the six row addresses are one parity offset plus constants.  The other
+//     form (issue_window_rows) reads the two rows under wave-uniform
+//     branches, so their registers stay live, undefined, on the paths that take the row from elsewhere and
 //     the merge costs a v_mov per value (26 per interior wave-step, 12 zero
 //     moves more per off-grid or neighbour row).  (A single row of zeros
 //     behind the buffers, with each row's offset chosen by scalar selects ahead
@@ -522,12 +501,7 @@ __device__ __forceinline__ void belief_any_pre(int u, int x0, uint32_t lx4, int 
 //   * the masked launch is never a shard's (no shard scale), and the publish
 //     tests its four role flags as bits of one SGPR instead of reloading four
 //     spilled lane-mask pairs with v_readlane_b32.
-#ifndef PP2_RES_LEAN
-#define PP2_RES_LEAN 1
-#endif
-// (it builds on the one-round-trip window reads)
-#define PP2_RES_LEAN_ON (PP2_RES_LEAN != 0 && PP2_RES_WINDOW1 != 0)
-// The lean instances' four tile buffers: rows of xs = tw + 4 floats (4 pad
+// The masked instances' four tile buffers: rows of xs = tw + 4 floats (4 pad
 // floats, then the row), buffer i's rows at row i (rt + 1) + 1 .., with a row
 // that is never written in front of every buffer and behind the last one.
 __host__ __device__ constexpr int lean_tile_floats(int rt, int tw) {
@@ -565,9 +539,10 @@ __device__ __forceinline__ void belief_masked(float wm, float ws, const float (&
     p[k] = (mk[k] == 0.0f ? own : p[k]) * lz[k];
   }
 }
-[[maybe_unused]] __device__ __forceinline__ void belief_any_masked(
-    int u, float wm, float ws, const float (&tc)[4], const float (&lz)[4], const float (&mk)[4],
-    const float (&bo)[4], const Win6& w, float (&p)[4]) {
+__device__ __forceinline__ void belief_any_masked(int u, float wm, float ws, const float (&tc)[4],
+                                                  const float (&lz)[4], const float (&mk)[4],
+                                                  const float (&bo)[4], const Win6& w,
+                                                  float (&p)[4]) {
   switch (u) {
 #define PP2_BQ(UU)                                        \
   case UU:                                                \
@@ -587,13 +562,26 @@ struct CentreSlots {
 };
 constexpr CentreSlots kCentreSlot{};
 
-// One window row (x0 - 1 .. x0 + 4) from a zero-padded LDS row: the lane's
-// aligned 16 B, and x0 - 1 / x0 + 4 from the neighbouring lanes' quads by DPP
-// wave shifts (wave_shr:1 / wave_shl:1; a wave holds 64 consecutive quads of
-// one row).  Lanes 0 and 63 have no source lane and keep the DPP's `old`
-// operand, the edge dword they read themselves (one 2-lane ds_read_b32 --
-// every lane reading its own edge dwords, at a 16-B lane stride, costs a
-// 4-way bank conflict per read).
+// One window row (x0 - 1 .. x0 + 4) from the lane's aligned quad m: x0 - 1 /
+// x0 + 4 come from the neighbouring lanes' quads by DPP wave shifts
+// (wave_shr:1 / wave_shl:1; a wave holds 64 consecutive quads of one row).
+// Lanes 0 and 63 have no source lane and keep the DPP's `old` operand, the
+// edge dword e of the lane's wave-edge neighbour.  (Q: an f4a read from LDS,
+// or the four floats of a neighbour's untagged granule.)
+template <class Q>
+__device__ __forceinline__ void window_row(const Q& m, float e, float (&v)[6]) {
+  v[0] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[3]),
+                                                    0x138, 0xf, 0xf, false));
+  v[1] = m[0]; v[2] = m[1]; v[3] = m[2]; v[4] = m[3];
+  v[5] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[0]),
+                                                    0x130, 0xf, 0xf, false));
+}
+// The same from a zero-padded LDS row: the lane's aligned 16 B, and the edge
+// dword that lanes 0 and 63 read themselves (one 2-lane ds_read_b32 -- every
+// lane reading its own edge dwords, at a 16-B lane stride, costs a 4-way bank
+// conflict per read).  (window_row's moves, written out: through the call the
+// PP2_RES_NOXCH build, whose timings DESIGN.md cites, gets other register
+// copies.)
 __device__ __forceinline__ void row_lds(const float* row, int x0, float (&v)[6]) {
   const float* p = row + x0;
   const f4a m = *reinterpret_cast<const f4a*>(p);
@@ -610,9 +598,9 @@ __device__ __forceinline__ void row_zero(float (&v)[6]) {
 #pragma unroll
   for (int i = 0; i < 6; ++i) v[i] = 0.0f;
 }
-// The whole-row instance's window rows in one LDS round trip
-// (PP2_RES_WINDOW1; A/B builds: 0 keeps three row_lds pairs).  row_lds per
-// row compiles to a dependent round trip per row: its 2-lane edge read is a
+// The whole-row instance's window rows in one LDS round trip.  row_lds per
+// row (the other instances' form) compiles to a dependent round trip per row:
+// its 2-lane edge read is a
 // save-exec region of its own, the DPP that takes the edge dword as `old`
 // follows it directly, and the scheduler moves no later row's reads across
 // the region -- three drains at the step's top, on every wave at once (all
@@ -623,24 +611,17 @@ __device__ __forceinline__ void row_zero(float (&v)[6]) {
 // class dwords and the action-0 records before them the step's top is one
 // issue burst and one wait.  An edge wave polls its neighbour's granules
 // between the two: its own rows land under the poll.
-// The edge dwords: 1 -- ONE exec-masked region (lanes 0 / 63), as
-// load_class_rows; 2 -- branch-free: lanes 0..31 read lane 0's dword and lanes
-// 32..63 lane 63's (two addresses, each a broadcast: no bank conflict), the
-// other lanes' copies are unused (a DPP's `old` counts on lanes 0 / 63 only).
+// The edge dwords are read branch-free: lanes 0..31 read lane 0's dword and
+// lanes 32..63 lane 63's (two addresses, each a broadcast: no bank conflict),
+// the other lanes' copies are unused (a DPP's `old` counts on lanes 0 / 63
+// only).  (One exec-masked region of lanes 0 / 63, as load_class_rows, was at
+// or above this form in every repetition of the 400- and 2000-step launches and
+// of the sweep, profiles/r10/ab_resident_variants.txt.)
 // A row that is not in LDS (in0 / in2 false: a neighbour's, or off the grid)
-// reads row ty's dwords again, unused, instead of a branch inside the region.
+// reads row ty's dwords again, unused, instead of a branch.
 // The edge dwords the first DPPs consume (row ty - 1's, else row ty's) go out
 // last, so that the first wait is the only one (LDS returns in order).
-// (2 by A/B: at or below 1 in every repetition of the 400- and 2000-step launches and
-// of the sweep, profiles/r10/ab_resident_variants.txt)
-#ifndef PP2_RES_WINDOW1
-#define PP2_RES_WINDOW1 2
-#endif
-// (k_sweep_resident's J rows and its action-0 records likewise)
-#ifndef PP2_RES_SWEEP_WINDOW1
-#define PP2_RES_SWEEP_WINDOW1 PP2_RES_WINDOW1
-#endif
-#if PP2_RES_WINDOW1 != 0 || PP2_RES_SWEEP_WINDOW1 != 0
+// (k_sweep_resident's J rows and its action-0 records likewise.)
 // NP planes (the loop: b, J; the sweep: J): quads q and edge dwords e of
 // window rows 0 .. 2; p[k] is the lane's quad in row ty of plane k.
 template <int NP>
@@ -648,7 +629,7 @@ struct WinRows {
   f4a q[NP][3];
   float e[NP][3];
 };
-template <int MODE, int NP>
+template <int NP>
 __device__ __forceinline__ void issue_window_rows(const float* const (&p)[NP], int xs, bool in0,
                                                   bool in2, WinRows<NP>& w) {
   const int lane = threadIdx.x & 63;
@@ -664,25 +645,15 @@ __device__ __forceinline__ void issue_window_rows(const float* const (&p)[NP], i
   }
   const int o0 = in0 ? -xs : 0, o2 = in2 ? xs : 0;
   // rows 2, 1, then row 0 with plane 0 last
-  auto edges = [&](int eo) {
+  const int eo = lane < 32 ? -1 - 4 * lane : 4 + 4 * (63 - lane);
 #pragma unroll
-    for (int k = 0; k < NP; ++k) w.e[k][2] = p[k][o2 + eo];
+  for (int k = 0; k < NP; ++k) w.e[k][2] = p[k][o2 + eo];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) w.e[k][1] = p[k][eo];
+  for (int k = 0; k < NP; ++k) w.e[k][1] = p[k][eo];
 #pragma unroll
-    for (int k = NP - 1; k >= 0; --k) w.e[k][0] = p[k][o0 + eo];
-  };
-  if constexpr (MODE == 1) {
-#pragma unroll
-    for (int k = 0; k < NP; ++k)
-#pragma unroll
-      for (int r = 0; r < 3; ++r) w.e[k][r] = 0.0f;
-    if (lane == 0 || lane == 63) edges(lane == 0 ? -1 : 4);
-  } else {
-    edges(lane < 32 ? -1 - 4 * lane : 4 + 4 * (63 - lane));
-  }
+  for (int k = NP - 1; k >= 0; --k) w.e[k][0] = p[k][o0 + eo];
 }
-// PP2_RES_LEAN: the same reads without a branch.  base + ro[k][r] is the start
+// The masked instances: the same reads without a branch.  base + ro[k][r] is the start
 // of plane k's window row r (a wave-uniform offset: the tile row, or the row
 // of zeros), xq the lane's first cell and xe the edge cell of its half of the
 // wave (lanes 0..31: the wave's x - 1, lanes 32..63: its x + 256).  The order
@@ -703,15 +674,6 @@ __device__ __forceinline__ void issue_window_rows_lean(const float* base, const 
 #pragma unroll
   for (int k = 1; k >= 0; --k) w.e[k][0] = base[ro[k][0] + xe];
 }
-// window row r from the quads and edge dwords in hand (row_lds's DPP moves)
-__device__ __forceinline__ void window_row(const f4a& m, float e, float (&v)[6]) {
-  v[0] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[3]),
-                                                    0x138, 0xf, 0xf, false));
-  v[1] = m[0]; v[2] = m[1]; v[3] = m[2]; v[4] = m[3];
-  v[5] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[0]),
-                                                    0x130, 0xf, 0xf, false));
-}
-#endif
 
 // Edge-row hand-off by self-tagged words (MI355X_MICROARCH.md § visibility,
 // handoff-1to1: the data is the flag).  Every value handed over -- belief and
@@ -737,29 +699,12 @@ __device__ __forceinline__ int xch_gran(int ntiles, int wpr, int slot, int tl, i
                                         int k, int ln) {
   return (((((slot * ntiles + tl) * 2 + side) * wpr + w) * kResidentGranules + k) * 64 + ln) * 16;
 }
-// Same-XCD hand-offs (PP2_RES_XCD_PLAIN): a plain store keeps the line in
+// Same-XCD hand-offs: a plain store keeps the line in
 // the XCD's L2, so the neighbour's sc1 (L1-bypassing, L2-served) loads take
 // it there, where an sc1 store drops it and the reader fetches it over the
 // fabric (MI355X_MICROARCH.md, visibility table).  Only where every reader
 // of the granule runs on the producer's XCD: the tile -> XCD map of
 // xcd_remap (block b on XCD b % 8 owns a contiguous range of tiles).
-#ifndef PP2_RES_XCD_PLAIN
-#define PP2_RES_XCD_PLAIN 1
-#endif
-// The whole-row loop's early arrival (k_loop_resident, `early`): 0 the late
-// order, 1 a workgroup barrier before thread 0's add, 2 an LDS wave count
-// whose last adder signals.
-#ifndef PP2_RES_EARLY
-#define PP2_RES_EARLY 2
-#endif
-// The whole-row loop's reducing wave at a block start: 1 wave 0, 0 the
-// interior wave of the other instances.
-#ifndef PP2_RES_REDW0
-#define PP2_RES_REDW0 1
-#endif
-#ifndef PP2_RES_XCD_AUX
-#define PP2_RES_XCD_AUX 0  // the same-XCD stores' cache policy (0 plain, 1 sc0, 2 nt)
-#endif
 __device__ __forceinline__ int tile_xcd(int t, int n) {
   const int q = n / 8, r = n % 8;
   return t < r * (q + 1) ? t / (q + 1) : r + (q > 0 ? (t - r * (q + 1)) / q : 0);
@@ -769,7 +714,7 @@ __device__ __forceinline__ void st_quad_x(Rsrc r, int off, const float (&v)[4], 
   const unsigned m = bit << 31;
   const u4v t = {__float_as_uint(v[0]) | m, __float_as_uint(v[1]) | m, __float_as_uint(v[2]) | m,
                  __float_as_uint(v[3]) | m};
-  if (plain) __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, PP2_RES_XCD_AUX);
+  if (plain) __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, 0);
   else __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, kSc1);
 }
 __device__ __forceinline__ bool tagged(const u4v& g, unsigned m) {
@@ -878,16 +823,6 @@ __device__ __forceinline__ void take_rows_sides(Rsrc r, bool rows, int o, bool e
     asm volatile("" ::: "memory");
   }
 }
-// One window row from the lane's aligned quad m and the edge dword e of the
-// lane's wave-edge neighbour (lanes 0 / 63), the others by DPP wave shifts.
-__device__ __forceinline__ void row_quad(const float (&m)[4], float e, float (&v)[6]) {
-  v[0] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[3]),
-                                                    0x138, 0xf, 0xf, false));
-  v[1] = m[0]; v[2] = m[1]; v[3] = m[2]; v[4] = m[3];
-  v[5] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e), __float_as_int(m[0]),
-                                                    0x130, 0xf, 0xf, false));
-}
-
 template <int CAP>
 struct alignas(4) Trajectory {  // (read as words: CAP % 4 == 0)
   static_assert(CAP % 4 == 0, "the loop reads the trajectory as 32-bit words");
@@ -906,13 +841,11 @@ struct alignas(4) Trajectory {  // (read as words: CAP % 4 == 0)
 // TC = 3: the 2-D tiling (2 tile columns) with at most 768 threads -- 3 waves
 // per SIMD, so a 168-VGPR budget instead of 128: the sweep's table reads of
 // all 4 cells of an action in flight together (coded_sweep_iw G = 4).
-// MW: empty, or one ResidentMasked -- the masked-support form (PP2_RES_MASKED;
-// the whole-row instance only) with its weights as a third kernel argument
-// (the other instances' arguments are the two they were).
+// MW: empty, or one ResidentMasked -- the masked-support form (the whole-row
+// instance only) with its weights as a third kernel argument (the other
+// instances' arguments are the two they were).
 __device__ __forceinline__ ResidentMasked masked_arg() { return ResidentMasked{}; }
-[[maybe_unused]] __device__ __forceinline__ ResidentMasked masked_arg(const ResidentMasked& m) {
-  return m;
-}
+__device__ __forceinline__ ResidentMasked masked_arg(const ResidentMasked& m) { return m; }
 template <int CAP, int TC, bool LAG, bool TR, class... MW>
 __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_resident(
     const ResidentHead a, const Trajectory<CAP> tr, const MW... mwa) {
@@ -930,10 +863,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   const int wp = a.g.wp, rows = a.g.rows, tw = wp / tc;
   const int tpr = tw >> 2, wpr = tw >> 8;  // lanes, waves per tile row
   const int xs = tw + 4;                // padded LDS row stride
-  // (kLean: a buffer's rows and the never-written row in front of them,
-  // lean_tile_floats)
-  constexpr bool kLean = MSK && PP2_RES_LEAN_ON;
-  const int bufn = kLean ? (a.rt + 1) * xs : 4 + a.rt * xs;  // one padded tile buffer
+  // one padded tile buffer (MSK: a buffer's rows and the never-written row in
+  // front of them, lean_tile_floats)
+  const int bufn = MSK ? (a.rt + 1) * xs : 4 + a.rt * xs;
   // LDS: class tables (QR, LT: constant offsets), factored sweep rows (QT, CT:
   // constant offsets; IW), class planes, b buffers 0, 1, J buffers 0, 1
   const int prows = a.rt + 2, ps = tw + 8;
@@ -943,7 +875,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   float* sB0 = reinterpret_cast<float*>(sP) + lds_span(MSK ? kResGCn : 9 * prows * ps / 4);
   const float* sGC = reinterpret_cast<const float*>(sP);
   (void)sGC;
-  float* sS = sB0 + (kLean ? lean_tile_floats(a.rt, tw) : 4 * bufn);
+  float* sS = sB0 + (MSK ? lean_tile_floats(a.rt, tw) : 4 * bufn);
   float* sRed = sS + 16;  // (red_lds) the lagged block start's partials
 
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -984,14 +916,14 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   const int sbase = 2 * a.ntiles * 2 * (wp >> 8) * kResidentGranules * 64 * 16;  // side region
   unsigned* const err = a.sync + kResidentSyncErr;
   const Rsrc rx = make_rsrc(a.xch);
-  auto sbuf = [&](int k, int slot) { return sB0 + (2 * k + slot) * bufn + (kLean ? xs : 0) + 4; };
+  auto sbuf = [&](int k, int slot) { return sB0 + (2 * k + slot) * bufn + (MSK ? xs : 0) + 4; };
   // the boundary waves' hand-off: b and J of the lane's quad as two
   // self-tagged granules {b0..b3}, {j0..j3} in exchange slot `slot`
   // (whether the row granules' reader, tile -+ tc, shares this tile's XCD)
   const int myx = tile_xcd(tile, (int)gridDim.x);
-  const bool plain_up = PP2_RES_XCD_PLAIN && nb_up && tile_xcd(tile - tc, (int)gridDim.x) == myx;
-  const bool plain_dn = PP2_RES_XCD_PLAIN && nb_dn && tile_xcd(tile + tc, (int)gridDim.x) == myx;
-  // (kLean) the publish's role flags as bits of one SGPR: held as wave-uniform
+  const bool plain_up = nb_up && tile_xcd(tile - tc, (int)gridDim.x) == myx;
+  const bool plain_dn = nb_dn && tile_xcd(tile + tc, (int)gridDim.x) == myx;
+  // (MSK) the publish's role flags as bits of one SGPR: held as wave-uniform
   // bools each is a lane-mask pair for the whole run, spilled, and the publish
   // reloads them with v_readlane_b32 every step.  The empty asm keeps the
   // compiler from widening a bit to such a mask again.  (The flags of the
@@ -1000,7 +932,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   enum : unsigned { kRoleUp = 1, kRoleDn = 2, kRolePlainUp = 4, kRolePlainDn = 8 };
   unsigned role = 0u;  // (set with bnd, below)
   auto is = [&](unsigned bit, bool flag) {
-    if constexpr (kLean) {
+    if constexpr (MSK) {
       asm volatile("" : "+s"(role));
       return (role & bit) != 0u;
     }
@@ -1057,8 +989,8 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     if (rows_in) {
       const float mb[4] = {untag(g[0][0]), untag(g[0][1]), untag(g[0][2]), untag(g[0][3])};
       const float mj[4] = {untag(g[1][0]), untag(g[1][1]), untag(g[1][2]), untag(g[1][3])};
-      row_quad(mb, (el || er) ? untag(e[0]) : 0.0f, vb);
-      row_quad(mj, (el || er) ? untag(e[1]) : 0.0f, vj);
+      window_row(mb, (el || er) ? untag(e[0]) : 0.0f, vb);
+      window_row(mj, (el || er) ? untag(e[1]) : 0.0f, vj);
     }
     if (sd) {
 #pragma unroll
@@ -1069,7 +1001,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     }
   };
 
-  // (kLean) the same poll, the row's quads and edge dwords written over the
+  // (MSK) the same poll, the row's quads and edge dwords written over the
   // window registers that issue_window_rows_lean filled from the row of zeros
   auto take_q = [&](int slot, int tl, int side, unsigned bit, f4a& qb, float& eb, f4a& qj,
                     float& ej) {
@@ -1138,13 +1070,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   stage_rows(a.rfact, kResTab, lds);
   stage_rows(a.rows, rows_floats(a.E, true), sTC);
   if constexpr (MSK) stage_rows(a.rfact + kResGC, kResGCn, reinterpret_cast<float*>(sP));
-  // (kLean: every float of the buffers -- the pads, the rows between the
+  // (MSK: every float of the buffers -- the pads, the rows between the
   // buffers and a partial tile's rows below the grid, which no wave writes)
-  for (int i = threadIdx.x; !kLean && i < 4 * (a.rt + 1); i += blockDim.x) {
+  for (int i = threadIdx.x; !MSK && i < 4 * (a.rt + 1); i += blockDim.x) {
     const int buf = i / (a.rt + 1), r = i % (a.rt + 1);
     *reinterpret_cast<f4a*>(sB0 + buf * bufn + r * xs) = f4a{0.0f, 0.0f, 0.0f, 0.0f};
   }
-  if constexpr (kLean) {
+  if constexpr (MSK) {
     for (int i = threadIdx.x; 4 * i < lean_tile_floats(a.rt, tw); i += blockDim.x)
       *reinterpret_cast<f4a*>(sB0 + 4 * i) = f4a{0.0f, 0.0f, 0.0f, 0.0f};
   }
@@ -1227,13 +1159,13 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   }
   PP2_RP(4);
   ClassRegs creg;
-  if constexpr (TC == 3 && PP2_RES_HOIST) {
+  if constexpr (TC == 3) {
     __syncthreads();  // the class planes
     if (valid) load_class_regs(sP, prows, ps, ty, x0, creg);
   }
   if (prior_err != 0u) return;  // (uniform: before any global store)
   const bool bnd = nb_up || nb_dn || sd_l || sd_r;  // waves that cross CUs
-  if constexpr (kLean)
+  if constexpr (MSK)
     role = (unsigned)__builtin_amdgcn_readfirstlane(
         (int)((nb_up ? kRoleUp : 0u) | (nb_dn ? kRoleDn : 0u) | (plain_up ? kRolePlainUp : 0u) |
               (plain_dn ? kRolePlainDn : 0u)));
@@ -1262,7 +1194,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // or not its rows cross a tile edge)
   unsigned use[2] = {a.slot_use[0], a.slot_use[1] + 1u};
   PP2_RP(5);
-  if constexpr (kSweepPipe && PP2_RES_EARLY == 2) {
+  if constexpr (kSweepPipe) {
     if (threadIdx.x == 0) sS[1] = 0.0f;  // (the early arrivals' wave count)
   }
   // step 0's input mass (k_sum_finalize's tree: lane-strided quads in
@@ -1295,19 +1227,17 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   // interior one (row 1, not a side wave; SIMD 1) when the tile has interior
   // rows, so that the reduction overlaps the edge waves' hand-off and compute
   // instead of following them on wave 0 (an edge wave)
-  // The whole-row instance (PP2_RES_REDW0): wave 0 after all.  With the
+  // The whole-row instance: wave 0 after all.  With the
   // arrivals out early the chain that is left starts when the reducing wave
   // has computed its quad, and the tile's first row, which computes with
   // issue priority on rows the tile above published early, is done first
   // (an interior wave is among the last; the tile's last row waits longest).
-  const int redw = kSweepPipe && PP2_RES_REDW0 != 0 ? 0 : a.rt >= 3 && wpr >= 4 ? wpr + 1 : 0;
+  const int redw = kSweepPipe ? 0 : a.rt >= 3 && wpr >= 4 ? wpr + 1 : 0;
   unsigned arrivals = a.arrive_base;
-  // early arrivals, form (b): the tile's valid waves (each stores a partial)
+  // early arrivals: the tile's valid waves (each stores a partial)
   // and their LDS count so far, sS[1] (zeroed in the prologue)
   const unsigned nvw = kSweepPipe ? (unsigned)(std::min(a.rt, rows - trow * a.rt) * wpr) : 0u;
   unsigned early_n = 0u;
-  (void)nvw;
-  (void)early_n;
   int shift = 0;  // shard runs: the power-of-two shifts of the block starts so far
   // Lagged shard block starts (shard mode 2; shards run kstep0 = 0, so block
   // starts fall on multiples of depth).  The shift of the block start at T
@@ -1353,19 +1283,12 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
   uint32_t uzw = trw[0];
   // (kstep0 + t) % depth, advanced per step
   int ph = a.kstep0 % a.depth;
-  (void)trw;
-  (void)uzw;
-  (void)ph;
-  // (kLean) the edge cell of the lane's half of the wave (issue_window_rows_lean)
-  const int xe = kLean ? wj * 256 + (lane < 32 ? -1 : 256) : 0;
+  // (MSK) the edge cell of the lane's half of the wave (issue_window_rows_lean)
+  const int xe = MSK ? wj * 256 + (lane < 32 ? -1 : 256) : 0;
   (void)xe;
   for (int t = 0; t < a.n; ++t) {
-#if PP2_RES_TRAJ_SGPR
     const uint32_t uzb = (uzw >> (8 * (t & 3))) & 0xffu;
     const int u = uzb & 15, z = uzb >> 4;
-#else
-    const int u = tr.uz[t] & 15, z = tr.uz[t] >> 4;
-#endif
     const int ci = t & 1, co = ci ^ 1;
     const bool last = t == a.n - 1;
     // ---- a block start inside the run needs the exact mass of step t-1's
@@ -1374,12 +1297,8 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     // than the owned ones).  The step's gather and backup go first: the mass
     // only scales the gathered quad, so the grid-wide arrival wait overlaps
     // this tile's compute instead of preceding it.
-#if PP2_RES_PHASE_CTR
     const bool bs = t > 0 && ph == 0;
     ph = ph + 1 == a.depth ? 0 : ph + 1;  // step t + 1's phase
-#else
-    const bool bs = t > 0 && (a.kstep0 + t) % a.depth == 0;
-#endif
     if (t > 0 && !bs) inv = 1.0f;
     if (lag) {
       if (wave == redw) {
@@ -1420,11 +1339,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     // loop, so the whole-row instance computes no mass partial on the other
     // steps.  (The other instances keep the partial per step: the change was
     // timed on the whole-row instance only.)
-#if PP2_RES_PHASE_CTR
     const bool arrive = ph == 0;
-#else
-    const bool arrive = (a.kstep0 + t + 1) % a.depth == 0;
-#endif
     const bool mass = !kSweepPipe || arrive || last;
     // ---- early arrival (the whole-row instance).  On an arrive step whose
     // belief is not scaled (no block start, not a launch's first step with a
@@ -1449,8 +1364,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
     //   * no new wait: the error word and the bounded waits work as before.
     // A step that is both arrive and block start (depth 1), the scaled first
     // step and the last step keep the late order.
-    const bool early = kSweepPipe && PP2_RES_EARLY != 0 && arrive && !bs && !last &&
-                       !(t == 0 && start0);
+    const bool early = kSweepPipe && arrive && !bs && !last && !(t == 0 && start0);
     auto early_arrive = [&]() {
       float s = 0.0f;
 #pragma unroll
@@ -1460,16 +1374,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         st_flag(reinterpret_cast<unsigned*>(a.ring + (size_t)(t % kResidentRing) * a.nparts + pi),
                 __float_as_uint(v));
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if PP2_RES_EARLY == 1
-      // (a) a workgroup barrier, then thread 0's add.  The tile's invalid
-      // waves (a partial last tile) join the barrier below, outside valid.
-      __syncthreads();
-      if (threadIdx.x == 0)
-        __hip_atomic_fetch_add(a.sync + kResidentSyncArrive, 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-#else
-      // (b) each valid wave counts itself in LDS after its drain; the wave
-      // whose add comes last (the tile's nvw-th of this step) signals
+      // each valid wave counts itself in LDS after its drain; the wave whose
+      // add comes last (the tile's nvw-th of this step) signals.  (No barrier:
+      // a partial last tile's invalid waves never come here.)
       early_n += nvw;
       if (lane == 0) {
         const unsigned old = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(sS + 1), 1u,
@@ -1479,9 +1386,8 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
                                  __HIP_MEMORY_SCOPE_AGENT);
       }
       asm volatile("" ::: "memory");
-#endif
     };
-    // (kLean) the step's masked J quad, best * mk: stored by step_quad,
+    // (MSK) the step's masked J quad, best * mk: stored by step_quad,
     // published by finish_quad
     float jmq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     (void)jmq;
@@ -1528,8 +1434,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         if (last) masked_sweep_pipe_begin<4, true>(sGC, iwr, mrec);
         else masked_sweep_pipe_begin<4, false>(sGC, iwr, mrec);
       }
-#if PP2_RES_WINDOW1 != 0
-      if constexpr (kLean) {
+      if constexpr (MSK) {
         // the same burst without a branch or a select: rows ty - 1 and ty + 1
         // of a buffer are there for every wave -- a tile row, or zeros (the row
         // in front of the buffer, the one behind it, a partial tile's row
@@ -1559,7 +1464,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         const bool in0 = ty > 0, in2 = ty + 1 < a.rt && y + 1 < rows;
         WinRows<2> wr;
         const float* const wp2[2] = {sbuf(0, ci) + ty * xs + x0, sbuf(1, ci) + ty * xs + x0};
-        issue_window_rows<PP2_RES_WINDOW1>(wp2, xs, in0, in2, wr);
+        issue_window_rows(wp2, xs, in0, in2, wr);
         __builtin_amdgcn_sched_barrier(0);
         if (in0) {
           window_row(wr.q[0][0], wr.e[0][0], wb.v[0]);
@@ -1581,9 +1486,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
           row_zero(wb.v[2]);
           row_zero(wj.v[2]);
         }
-      } else
-#endif
-      {
+      } else {
         if (ty > 0) {
           row_lds(sbuf(0, ci) + (ty - 1) * xs, x0, wb.v[0]);
           row_lds(sbuf(1, ci) + (ty - 1) * xs, x0, wj.v[0]);
@@ -1619,7 +1522,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         }
       }
       PP2_RT(1);
-      if constexpr (TC == 3 && PP2_RES_HOIST) {
+      if constexpr (TC == 3) {
         // opaque per step (empty asm): otherwise the compiler hoists the 9
         // actions' table addresses, loop-invariant now, out of the step loop
 #pragma unroll
@@ -1631,15 +1534,11 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       else if constexpr (MSK) {
         const float bo[4] = {p[0], p[1], p[2], p[3]};
         belief_any_masked(u, mw.w_main, mw.w_side, tcv, lzv, mk, bo, wb, p);
-        if constexpr (PP2_RES_EARLY != 0) {
-          if (early) early_arrive();
-        }
+        if (early) early_arrive();
       }
       else if constexpr (kSweepPipe) {
         belief_any_pre<TR>(u, x0, lx4, z, wb, crow, p);
-        if constexpr (PP2_RES_EARLY != 0) {
-          if (early) early_arrive();
-        }
+        if (early) early_arrive();
       }
       else belief_any<TR>(u, sP, prows, ps, ty, x0, lx4, z, wb, p);
       float jn[9][4];  // grid stencil offset i = 3 (dy + 1) + dx + 1
@@ -1659,16 +1558,12 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         for (int k = 0; k < 4; ++k) {
           const bool blocked = mk[k] == 0.0f;
           best[k] = blocked ? ov[k] : best[k];
-          if (!kLean || last) arg[k] = blocked ? 0u : arg[k];  // (stored by the last step alone)
+          if (last) arg[k] = blocked ? 0u : arg[k];  // (stored by the last step alone)
         }
-        if constexpr (kLean) {  // (finish_quad publishes the same quad)
+        // (finish_quad publishes the same quad)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) jmq[k] = best[k] * mk[k];
-          *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) = f4a{jmq[0], jmq[1], jmq[2], jmq[3]};
-          return;
-        }
-        *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) =
-            f4a{best[0] * mk[0], best[1] * mk[1], best[2] * mk[2], best[3] * mk[3]};
+        for (int k = 0; k < 4; ++k) jmq[k] = best[k] * mk[k];
+        *reinterpret_cast<f4a*>(sbuf(1, co) + ty * xs + x0) = f4a{jmq[0], jmq[1], jmq[2], jmq[3]};
         return;
       } else if constexpr (kSweepPipe) {  // (actions: last step only)
         if (last) coded_sweep_iw_pipe_rest<4, true>(sTC, iwr, jn, rtv, rcost, best, arg);
@@ -1692,10 +1587,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         const float pm[4] = {p[0] * mk[0], p[1] * mk[1], p[2] * mk[2], p[3] * mk[3]};
         *reinterpret_cast<f4a*>(sbuf(0, co) + ty * xs + x0) = f4a{pm[0], pm[1], pm[2], pm[3]};
         if (bnd) {
-          float jm[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) jm[k] = kLean ? jmq[k] : best[k] * mk[k];
-          if (!last) publish(ci, pm, jm, (use[ci] + 1u) & 1u);
+          if (!last) publish(ci, pm, jmq, (use[ci] + 1u) & 1u);
           __builtin_amdgcn_s_setprio(0);
         }
         return;
@@ -1713,9 +1605,6 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       step_quad();
       if (!bs || lag) finish_quad();
     }
-#if PP2_RES_EARLY == 1
-    else if (early) __syncthreads();  // early_arrive's barrier (a wave-uniform branch)
-#endif
     if (bs && !lag) {
       if (wave == redw) {
         arrivals += a.ntiles;
@@ -1725,7 +1614,7 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
         if (lane == 0) sS[0] = S;
       }
       __syncthreads();
-      if (!kLean && a.shard) {  // (the masked launch is never a shard's)
+      if (!MSK && a.shard) {  // (the masked launch is never a shard's)
         const int sh = pow2_shift(sS[0]);
         shift += sh;
         inv = pow2f(sh);
@@ -1763,11 +1652,9 @@ __global__ __launch_bounds__(TC == 3 ? 768 : 1024, TC == 3 ? 3 : 4) void k_loop_
       }
       if (lane == 0) sS[0] = S;
     }
-#if PP2_RES_TRAJ_SGPR
     // steps t + 1 .. t + 4's word, under the barrier's wait (after the backup:
     // a scalar load among its counted lgkmcnt waits would make them drains)
     if (((t + 1) & 3) == 0 && t + 1 < CAP) uzw = trw[(t + 1) >> 2];
-#endif
 #ifndef PP2_RES_NOBAR
     __syncthreads();  // also: this step's LDS writes before the next step's reads
 #endif
@@ -1837,8 +1724,8 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
   auto sbuf = [&](int i) { return sJ0 + i * bufn + 4; };
   // k_loop_resident's hand-off with J alone: granule 0, {j0..j3}
   const int myx = tile_xcd(tile, (int)gridDim.x);
-  const bool plain_up = PP2_RES_XCD_PLAIN && nb_up && tile_xcd(tile - 1, (int)gridDim.x) == myx;
-  const bool plain_dn = PP2_RES_XCD_PLAIN && nb_dn && tile_xcd(tile + 1, (int)gridDim.x) == myx;
+  const bool plain_up = nb_up && tile_xcd(tile - 1, (int)gridDim.x) == myx;
+  const bool plain_dn = nb_dn && tile_xcd(tile + 1, (int)gridDim.x) == myx;
   auto publish = [&](int slot, const float (&j)[4], unsigned bit) {
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
@@ -1858,7 +1745,7 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
     unsigned e[1];
     take_granules(rx, o, el || er, eo, bit, g, e, err, a.err_host);
     const float m[4] = {untag(g[0][0]), untag(g[0][1]), untag(g[0][2]), untag(g[0][3])};
-    row_quad(m, (el || er) ? untag(e[0]) : 0.0f, v);
+    window_row(m, (el || er) ? untag(e[0]) : 0.0f, v);
   };
 
   stage_rows(a.rows, rows_floats(a.E, true), sTC);
@@ -1907,7 +1794,6 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
     if (valid) {
       if (nb_up || nb_dn) __builtin_amdgcn_s_setprio(2);
       Win6 w;
-#if PP2_RES_SWEEP_WINDOW1 != 0
       // k_loop_resident's step top: the records of action 0 and every LDS
       // read of the window rows in one issue burst, before a neighbour's poll.
       // (One body per ARG: with begin and rest under two branches of their
@@ -1920,7 +1806,7 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
         const bool in0 = ty > 0, in2 = ty + 1 < a.rt && y + 1 < rows;
         WinRows<1> wr;
         const float* const wp1[1] = {sbuf(ci) + ty * xs + x0};
-        issue_window_rows<PP2_RES_SWEEP_WINDOW1>(wp1, xs, in0, in2, wr);
+        issue_window_rows(wp1, xs, in0, in2, wr);
         __builtin_amdgcn_sched_barrier(0);
         if (in0) window_row(wr.q[0][0], wr.e[0][0], w.v[0]);
         else if (nb_up) take(co, tile - 1, 1, use[co] & 1u, w.v[0]);
@@ -1938,22 +1824,6 @@ __global__ __launch_bounds__(1024, 4) void k_sweep_resident(const SweepRun a) {
       };
       if (check || fin) sweep_quad(std::true_type{});
       else sweep_quad(std::false_type{});
-#else
-      if (ty > 0) row_lds(sbuf(ci) + (ty - 1) * xs, x0, w.v[0]);
-      else if (nb_up) take(co, tile - 1, 1, use[co] & 1u, w.v[0]);
-      else row_zero(w.v[0]);
-      row_lds(sbuf(ci) + ty * xs, x0, w.v[1]);
-      if (ty + 1 < a.rt && y + 1 < rows) row_lds(sbuf(ci) + (ty + 1) * xs, x0, w.v[2]);
-      else if (nb_dn) take(co, tile + 1, 0, use[co] & 1u, w.v[2]);
-      else row_zero(w.v[2]);
-      float jn[9][4];
-#pragma unroll
-      for (int i = 0; i < 9; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) jn[i][k] = w.v[i / 3][k + i % 3];
-      if (check || fin) coded_sweep_iw_pipe<4, true>(sTC, iwr, jn, best, arg);
-      else coded_sweep_iw_pipe<4, false>(sTC, iwr, jn, best, arg);
-#endif
       *reinterpret_cast<f4a*>(sbuf(co) + ty * xs + x0) = f4a{best[0], best[1], best[2], best[3]};
       if (nb_up || nb_dn) {
         publish(ci, best, (use[ci] + 1u) & 1u);
@@ -2030,25 +1900,72 @@ size_t resident_lds_bytes(const Geom& g, int E, int rt, int tc) {
 
 size_t resident_masked_lds_bytes(const Geom& g, int E, int rt) {
   return ((size_t)lds_span(kResTab) + lds_span(rows_floats(E, true)) + lds_span(kResGCn) +
-          (PP2_RES_LEAN_ON ? (size_t)lean_tile_floats(rt, g.wp)
-                                                     : 4 * (4 + (size_t)rt * (g.wp + 4))) +
-          16) *
+          (size_t)lean_tile_floats(rt, g.wp) + 16) *
          sizeof(float);
 }
 
-bool resident_masked_built() { return PP2_RES_MASKED != 0; }
+// The kernel instance of a tiling: 2-D tiles of <= 768 threads run the
+// register-rich TC = 3 instance.
+static int resident_tc(int tc, int threads) { return tc == 2 && threads <= 768 ? 3 : tc; }
+
+// One instantiation of k_loop_resident: its address and once-per-device
+// allow_lds flag for the planner, its typed launch for the launcher.
+template <int CAP, int TC, bool LAG, bool TR, class... MW>
+struct ResidentInstance {
+  static constexpr bool kMasked = sizeof...(MW) != 0;
+  static const void* fn() {
+    return reinterpret_cast<const void*>(&k_loop_resident<CAP, TC, LAG, TR, MW...>);
+  }
+  static unsigned long long& lds_allowed() {
+    static unsigned long long done = 0;
+    return done;
+  }
+  // Runs of at most kResidentShortSteps steps: the rest of the argument is 0.
+  static void launch(hipStream_t st, const ResidentPlan& p, size_t lds, const ResidentRun& a,
+                     const MW&... mw) {
+    const ResidentHead& h = a;
+    Trajectory<CAP> tr;
+    if constexpr (CAP == kResidentShortSteps) {
+      tr = Trajectory<CAP>{};
+      std::memcpy(tr.uz, a.uz, (size_t)a.n);
+    } else {
+      std::memcpy(tr.uz, a.uz, sizeof tr.uz);
+    }
+    hipLaunchKernelGGL((k_loop_resident<CAP, TC, LAG, TR, MW...>), dim3(p.ntiles), dim3(p.threads),
+                       lds, st, h, tr, mw...);
+  }
+};
+// The 18 instances, named in one place: f(the ResidentInstance) for a run of n
+// steps (the short or the long trajectory argument) on the tiling's instance
+// -- transposed tiles, else ktc = resident_tc(...) in {1, 2, 3} -- with lagged
+// block starts or not; masked: the masked-support form of the whole-row
+// instance (ktc == 1, neither transposed nor lagged: the callers check).
+// (The code object holds the kernels in the order they are named here:
+// unlagged before lagged, short before long, the masked pair last.)
+template <class F>
+static auto with_resident_instance(int n, int ktc, bool lag, bool trn, bool masked, F&& f) {
+  constexpr int S = kResidentShortSteps, L = kResidentMaxSteps;
+  const bool shrt = n <= S;
+  auto tiling = [&](auto cap, auto lg) {
+    constexpr int C = decltype(cap)::value;
+    constexpr bool G = decltype(lg)::value;
+    if (trn) return f(ResidentInstance<C, 1, G, true>{});
+    if (ktc == 1) return f(ResidentInstance<C, 1, G, false>{});
+    if (ktc == 2) return f(ResidentInstance<C, 2, G, false>{});
+    return f(ResidentInstance<C, 3, G, false>{});
+  };
+  auto steps = [&](auto lg) {
+    if (shrt) return tiling(std::integral_constant<int, S>{}, lg);
+    return tiling(std::integral_constant<int, L>{}, lg);
+  };
+  if (!masked && !lag) return steps(std::false_type{});
+  if (!masked) return steps(std::true_type{});
+  if (shrt) return f(ResidentInstance<S, 1, false, false, ResidentMasked>{});
+  return f(ResidentInstance<L, 1, false, false, ResidentMasked>{});
+}
 
 // The plan with tc tile columns: rt rows per tile so that the tiles fit the
 // CUs, or false.
-// The kernel instance of a tiling: 2-D tiles of <= 768 threads run the
-// register-rich TC = 3 instance (PP2_RES_RICH=0 at build time: never).
-static int resident_tc(int tc, int threads) {
-#ifndef PP2_RES_RICH
-#define PP2_RES_RICH 1
-#endif
-  return tc == 2 && threads <= 768 && PP2_RES_RICH ? 3 : tc;
-}
-
 static bool resident_plan_tc(const Geom& g, int E, int ncus, int tc, ResidentPlan* p,
                              bool trn = false) {
   if (tc < 1 || tc > 2 || g.wp % (256 * tc) != 0 || (tc > 1 && g.wp / tc < 512) || ncus < tc) return false;
@@ -2058,54 +1975,33 @@ static bool resident_plan_tc(const Geom& g, int E, int ncus, int tc, ResidentPla
   const size_t lds = resident_lds_bytes(g, E, rt, tc);
   if (lds > kDictLdsMaxBytes) return false;
   if (trn && tc != 1) return false;
-  static unsigned long long attr[16] = {};
   // the instance: TC = 3 for 2-D tiles of <= 768 threads (resident_tc)
   const int ktc = resident_tc(tc, (int)threads);
-#define PP2_K(CAPV, TCV, LAGV, TRV) reinterpret_cast<const void*>(&k_loop_resident<CAPV, TCV, LAGV, TRV>)
-#define PP2_KT(CAPV, LAGV)                                                                    \
-  (trn ? PP2_K(CAPV, 1, LAGV, true)                                                           \
-       : ktc == 1 ? PP2_K(CAPV, 1, LAGV, false)                                               \
-                  : ktc == 2 ? PP2_K(CAPV, 2, LAGV, false) : PP2_K(CAPV, 3, LAGV, false))
-  const void* ks[4] = {PP2_KT(kResidentShortSteps, false), PP2_KT(kResidentMaxSteps, false),
-                       PP2_KT(kResidentShortSteps, true), PP2_KT(kResidentMaxSteps, true)};
-#undef PP2_KT
-#undef PP2_K
-  const int ai = trn ? 8 : 4 * (ktc - 1) + (ktc == 3 ? 4 : 0);
+  // every instance a launch on this plan can pick: the short and the long
+  // trajectory, with and without lagged block starts, and the masked-support
+  // pair of an untransposed whole-row plan (less LDS: no class planes; the
+  // tiling is the plan's)
   int nb = 1 << 30;
-  for (int k = 0; k < 4; ++k) {
-    allow_lds(ks[k], attr[ai + k]);
-    int n1 = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, ks[k], (int)threads, lds) != hipSuccess ||
-        n1 < 1) {
-      (void)hipGetLastError();
-      return false;
-    }
-    nb = std::min(nb, n1);
-  }
-#if PP2_RES_MASKED
-  // the masked-support instances of a whole-row plan (less LDS: no class
-  // planes; the tiling is the plan's)
-  if (ktc == 1 && !trn) {
-    static unsigned long long mattr[2] = {};
-    const void* km[2] = {
-        reinterpret_cast<const void*>(
-            &k_loop_resident<kResidentShortSteps, 1, false, false, ResidentMasked>),
-        reinterpret_cast<const void*>(
-            &k_loop_resident<kResidentMaxSteps, 1, false, false, ResidentMasked>)};
-    for (int k = 0; k < 2; ++k) {
-      allow_lds(km[k], mattr[k]);
+  auto fits = [&](int n, bool lag, bool masked) {
+    return with_resident_instance(n, ktc, lag, trn, masked, [&](auto inst) {
+      allow_lds(inst.fn(), inst.lds_allowed());
       int n1 = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, km[k], (int)threads,
-                                                       resident_masked_lds_bytes(g, E, rt)) !=
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+              &n1, inst.fn(), (int)threads, masked ? resident_masked_lds_bytes(g, E, rt) : lds) !=
               hipSuccess ||
           n1 < 1) {
         (void)hipGetLastError();
         return false;
       }
       nb = std::min(nb, n1);
-    }
-  }
-#endif
+      return true;
+    });
+  };
+  const int ns = kResidentShortSteps, nl = kResidentMaxSteps;
+  if (!fits(ns, false, false) || !fits(nl, false, false) || !fits(ns, true, false) ||
+      !fits(nl, true, false))
+    return false;
+  if (ktc == 1 && !trn && (!fits(ns, false, true) || !fits(nl, false, true))) return false;
   p->rt = rt;
   p->tc = tc;
   p->tr = trn;
@@ -2153,7 +2049,6 @@ hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const Res
       a.own0 >= a.own1 || a.b_out == a.b_in || a.j_out == a.j_in ||
       (a.in_partials && a.in_partials == a.out_partials))
     return hipErrorInvalidValue;
-  const ResidentHead& h = a;
   const size_t lds = p.lds + (a.red_lds ? (size_t)kResRedFloats * sizeof(float) : 0);
   if (a.red_lds && (a.shard != 2 || a.kstep0 != 0 || a.nparts > kResRedFloats || lds > kDictLdsMaxBytes))
     return hipErrorInvalidValue;
@@ -2163,53 +2058,14 @@ hipError_t launch_loop_resident(hipStream_t st, const ResidentPlan& p, const Res
   if (lag && 3 * a.depth + 1 >= kResidentRing) return hipErrorInvalidValue;
   if (p.tr && (p.tc != 1 || !a.shard || a.own0 % 4 != 0 || a.own1 % 4 != 0 || a.ows < a.g.rows))
     return hipErrorInvalidValue;
-#define PP2_RES_LAUNCH(CAPV, TCV, TRV)                                                           \
-  do {                                                                                           \
-    if (lag)                                                                                     \
-      hipLaunchKernelGGL((k_loop_resident<CAPV, TCV, true, TRV>), dim3(p.ntiles),                \
-                         dim3(p.threads), lds, st, h, tr);                                       \
-    else                                                                                         \
-      hipLaunchKernelGGL((k_loop_resident<CAPV, TCV, false, TRV>), dim3(p.ntiles),               \
-                         dim3(p.threads), lds, st, h, tr);                                       \
-  } while (0)
   const int ktc = resident_tc(p.tc, p.threads);
-  if (masked) {
-#if PP2_RES_MASKED
-    if (ktc != 1 || p.tr || lag || a.shard || a.red_lds) return hipErrorInvalidValue;
-    const size_t mlds = resident_masked_lds_bytes(a.g, a.E, p.rt);
-    const ResidentMasked mw = *masked;
-    if (a.n <= kResidentShortSteps) {
-      Trajectory<kResidentShortSteps> tr{};
-      std::memcpy(tr.uz, a.uz, (size_t)a.n);
-      hipLaunchKernelGGL((k_loop_resident<kResidentShortSteps, 1, false, false, ResidentMasked>),
-                         dim3(p.ntiles), dim3(p.threads), mlds, st, h, tr, mw);
-    } else {
-      Trajectory<kResidentMaxSteps> tr;
-      std::memcpy(tr.uz, a.uz, sizeof tr.uz);
-      hipLaunchKernelGGL((k_loop_resident<kResidentMaxSteps, 1, false, false, ResidentMasked>),
-                         dim3(p.ntiles), dim3(p.threads), mlds, st, h, tr, mw);
-    }
-    return hipGetLastError();
-#else
-    return hipErrorInvalidValue;
-#endif
-  }
-  if (a.n <= kResidentShortSteps) {
-    Trajectory<kResidentShortSteps> tr{};
-    std::memcpy(tr.uz, a.uz, (size_t)a.n);
-    if (p.tr) PP2_RES_LAUNCH(kResidentShortSteps, 1, true);
-    else if (ktc == 1) PP2_RES_LAUNCH(kResidentShortSteps, 1, false);
-    else if (ktc == 2) PP2_RES_LAUNCH(kResidentShortSteps, 2, false);
-    else PP2_RES_LAUNCH(kResidentShortSteps, 3, false);
-  } else {
-    Trajectory<kResidentMaxSteps> tr;
-    std::memcpy(tr.uz, a.uz, sizeof tr.uz);
-    if (p.tr) PP2_RES_LAUNCH(kResidentMaxSteps, 1, true);
-    else if (ktc == 1) PP2_RES_LAUNCH(kResidentMaxSteps, 1, false);
-    else if (ktc == 2) PP2_RES_LAUNCH(kResidentMaxSteps, 2, false);
-    else PP2_RES_LAUNCH(kResidentMaxSteps, 3, false);
-  }
-#undef PP2_RES_LAUNCH
+  if (masked && (ktc != 1 || p.tr || lag || a.shard || a.red_lds)) return hipErrorInvalidValue;
+  with_resident_instance(a.n, ktc, lag, p.tr, masked != nullptr, [&](auto inst) {
+    if constexpr (decltype(inst)::kMasked)
+      inst.launch(st, p, resident_masked_lds_bytes(a.g, a.E, p.rt), a, *masked);
+    else
+      inst.launch(st, p, lds, a);
+  });
   return hipGetLastError();
 }
 

@@ -1391,8 +1391,7 @@ static int loop_resident(pp2_ctx* c, int n, const uint8_t* us, const uint8_t* zs
     for (int k = 0; k < m; ++k) a.uz[k] = (uint8_t)(us[i + k] | (zs[i + k] << 4));
     a.err_host = journal(c, 1, m, us + i, zs + i);
     // the masked-support instance: whole-row tiles of an admitted model
-    const bool msk = c->dict_masked && c->res_masked && p.tc == 1 && !p.tr &&
-                     pp2::resident_masked_built();
+    const bool msk = c->dict_masked && c->res_masked && p.tc == 1 && !p.tr;
     CHECK(gated_launch(c, [&] {
       return pp2::launch_loop_resident(c->stream, p, a, msk ? &c->res_mw : nullptr);
     }));

@@ -1,5 +1,6 @@
 """GPU: the masked whole-row instances without their non-arithmetic VALU work
-(pp2_resident.hip, PP2_RES_LEAN): every window row is read from LDS into the
+(pp2_resident.hip, issue_window_rows_lean and take_q of the ResidentMasked
+instances of k_loop_resident): every window row is read from LDS into the
 same registers whatever its source -- the tile's row, a never-written row of
 zeros in front of or behind the tile buffer for a row that is off the grid, the
 neighbour tile's granules OR-ed over those zeros -- and the masked J quad is

@@ -1,5 +1,6 @@
 """GPU: the masked-support form of the resident loop's whole-row instance
-(pp2_resident.hip, PP2_RES_MASKED; admission: pp2_masked.h).  The tile's LDS
+(pp2_resident.hip, k_loop_resident<CAP, 1, false, false, ResidentMasked>;
+admission: pp2_masked.h).  The tile's LDS
 planes and the exchanged granules hold b and J with blocked cells stored as +0,
 an off-centre weight is one of two constants of the kernel's head, the gather
 reads the cells' centre T and L_z alone and the backup one 8-B record per

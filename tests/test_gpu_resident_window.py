@@ -1,4 +1,5 @@
-"""GPU: the top of the resident loop's step (pp2_resident.hip, PP2_RES_WINDOW1):
+"""GPU: the top of the resident loop's step (pp2_resident.hip,
+issue_window_rows and window_row in k_loop_resident and k_sweep_resident):
 the whole-row instance issues every LDS read of its window rows -- the b and J
 quads of the rows that live in the tile and the edge dwords of lanes 0 / 63 --
 in one burst behind the class dwords and the action-0 records, an edge wave

@@ -2,7 +2,7 @@
 resident_trace.sh): for tiles 1..15, wave 0 (the tile's first row: waits for
 the tile above) and wave 5 (an interior row at 1024^2), the median over steps
 8..63 of  top -> rows in hand -> computed+published -> after the barrier ->
-next top.  PP2_RES_HX picks the hand-off variant."""
+next top."""
 import ctypes as C
 import os
 import sys
@@ -34,7 +34,7 @@ def main():
         assert fn(buf.ctypes.data) == 0
     b = buf.astype(np.int64)
     tot = (b[1:, 56, 0, 0] - b[1:, 8, 0, 0]) / 100.0 / 48
-    print(f"N={N} prio={os.environ.get('PP2_RES_PRIO', '1')}: us/step (tiles 1..15, steps 8..56, "
+    print(f"N={N}: us/step (tiles 1..15, steps 8..56, "
           f"block starts included) median {np.median(tot):.2f}")
     names = ["top->rows", "rows->done", "done->barrier", "barrier->top"]
     for w, role in ((0, "row 0 (top edge) wave 0"), (1, "row 1 (interior) wave 5"),
