@@ -295,8 +295,8 @@ int pp2_model_dict_info(pp2_ctx* ctx, int* entries, int* active);
  * state flags of the sparse paths are neither cleared nor set.  Objects that
  * cached model data at creation refuse to run afterwards: pp2_planner_step of
  * a planner created before an update that changed the model returns
- * PP2_ESTATE (create a new one); rollouts and episode batches read the model
- * on every run and carry on. */
+ * PP2_ESTATE until pp2_planner_refresh brings its caches up to date; rollouts
+ * and episode batches read the model on every run and carry on. */
 int pp2_map_update(pp2_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                    const uint8_t* patch);
 int pp2_goal_set(pp2_ctx* ctx, int32_t gx, int32_t gy);
@@ -425,6 +425,16 @@ int pp2_fib_sweep(pp2_ctx* ctx, int n);
 /* fastInformedBound driver (fast_informed_bound_cuda.cu:206-276): blocks of
  * 10 sweeps until the inf-norm of the change <= 0.01. */
 int pp2_fib_solve(pp2_ctx* ctx, int max_sweeps, int* sweeps, float* final_norm);
+/* pp2_fib_solve without its pp2_fib_reset: the same blocks of 10 sweeps and
+ * the same stop rule, started from the current alphas (after pp2_map_update /
+ * pp2_goal_set: the previous solution).  The sweep is a contraction, so a
+ * warm start converges to the same fixed point as a cold one, within the stop
+ * rule's tolerance.  From alphas of 0 the iterates fall monotonically and each
+ * is an upper bound; from an arbitrary start they are not monotone, so after
+ * an update that removed an obstacle (values rise) the alphas need not be
+ * upper bounds before convergence.  The caller chooses: pp2_fib_resolve where
+ * fewer sweeps matter, pp2_fib_solve where every iterate must bound. */
+int pp2_fib_resolve(pp2_ctx* ctx, int max_sweeps, int* sweeps, float* final_norm);
 /* host_fib_alphas layout [hw][9] (fast_informed_bound_cuda.cu:270-271). */
 int pp2_fib_get(pp2_ctx* ctx, float* alphas);
 int pp2_fib_set(pp2_ctx* ctx, const float* alphas);
@@ -557,6 +567,48 @@ int pp2_planner_step(pp2_planner* p, uint8_t action, uint8_t observation,
 /* resetSearchTreeCallback (:275-282). */
 int pp2_planner_reset(pp2_planner* p);
 int pp2_planner_info(pp2_planner* p, pp2_tree_info* info);
+/* Brings a planner's cached model (its host copies of T and L, its dense R
+ * and L rows) up to the context's current model after pp2_map_update /
+ * pp2_goal_set; until then pp2_planner_step returns PP2_ESTATE.  With the
+ * model unchanged since the planner last read it: PP2_OK, nothing is launched,
+ * the tree is kept, the call counts nowhere.  Otherwise the caches are patched
+ * over the cells the updates regenerated (one kernel launch, one synchronise)
+ * when the context still remembers every update since (its journal holds the
+ * last 16), those rectangles hold at most 4096 cells together and
+ * PP2_TUNE_MAP_INCREMENTAL is 1 at the time of the call; else they are read
+ * again in full, as pp2_planner_create reads them.  Correctness never rests on
+ * the patch path.  Either way nothing is allocated besides the patch path's
+ * staging buffer on its first use.
+ *
+ * The tree was built under the old model: every node below the root is
+ * deleted.  The root's belief stays where it is, the same bits with the same
+ * mass, and becomes a fresh unexpanded root (depth 0) whose bounds are those
+ * of the current model, the current FIB alphas and, in lower_bound_mode 1, the
+ * current PBVI alphas: the caller re-solves them first (pp2_fib_resolve /
+ * pp2_fib_solve, ...), refresh uses whatever alphas are current.  The next
+ * pp2_planner_step(action, observation, NULL, ...) re-roots from that belief.
+ * Without a root (never stepped, or reset) only the caches are refreshed.  The
+ * rand() stream continues, the cuRAND uniforms and the parameters stay.  A
+ * changed PBVI set size is reported by the next step.
+ *
+ * pp2_model_upload does not count as an update: it leaves a planner's caches
+ * stale without any refusal, and refresh sees nothing to do (existing
+ * behaviour; create the planner after the upload). */
+int pp2_planner_refresh(pp2_planner* p);
+/* Diagnostics: refreshes that found a changed model, those of them served by
+ * the patch path, those that read the caches in full, and the cells the last
+ * such refresh patched (rectangles of several updates that overlap count a
+ * cell once each; 0 after a full one).  Any pointer may be NULL. */
+int pp2_planner_refresh_info(pp2_planner* p, long long* refreshes, long long* incremental,
+                             long long* full, long long* cells_patched);
+/* The root's belief (hw floats) as a new tree would be given it: under
+ * reference_order 1 the root's normalised row bit for bit, under
+ * reference_order 0 the stored belief divided by its stored mass (IEEE
+ * division on the host).  PP2_ESTATE without a root.  Synchronises. */
+int pp2_planner_root_belief(pp2_planner* p, float* belief);
+/* rand_skip plus every rand() draw the planner has taken: the rand_skip a
+ * planner created now needs to continue the same stream. */
+int pp2_planner_rand_calls(pp2_planner* p, uint64_t* calls);
 /* The 2*n curand_uniform draws the reference's cudaForwardSampling sees:
  * u1[i], u2[i] = first and second draw of curand_init(seed, i, 0). */
 int pp2_curand_uniforms(uint64_t seed, int n, float* u1, float* u2);

@@ -90,6 +90,7 @@ SIGNATURES = {
     "pp2_fib_reset": [_vp],
     "pp2_fib_sweep": [_vp, C.c_int],
     "pp2_fib_solve": [_vp, C.c_int, _i32p, _f32p],
+    "pp2_fib_resolve": [_vp, C.c_int, _i32p, _f32p],
     "pp2_fib_get": [_vp, _f32p],
     "pp2_fib_set": [_vp, _f32p],
     "pp2_fib_save": [_vp, C.c_char_p],
@@ -111,6 +112,11 @@ SIGNATURES = {
     "pp2_planner_step": [_vp, C.c_uint8, C.c_uint8, _f32p, _u8p, _f32p],
     "pp2_planner_reset": [_vp],
     "pp2_planner_info": [_vp, _vp],
+    "pp2_planner_refresh": [_vp],
+    "pp2_planner_refresh_info": [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                 C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+    "pp2_planner_root_belief": [_vp, _f32p],
+    "pp2_planner_rand_calls": [_vp, C.POINTER(C.c_uint64)],
     "pp2_curand_uniforms": [C.c_uint64, C.c_int, _f32p, _f32p],
     "pp2_rollout_create": [C.POINTER(_vp), _vp, C.c_int, C.c_int],
     "pp2_rollout_destroy": [_vp],

@@ -359,6 +359,13 @@ class GridContext:
         call("pp2_fib_solve", self._h, int(max_sweeps), C.byref(s), C.byref(nrm))
         return s.value, nrm.value
 
+    def fib_resolve(self, max_sweeps: int = 0):
+        """``fib_solve`` from the current alphas instead of 0 (pp2_fib_resolve)."""
+        s = C.c_int()
+        nrm = C.c_float()
+        call("pp2_fib_resolve", self._h, int(max_sweeps), C.byref(s), C.byref(nrm))
+        return s.value, nrm.value
+
     def fib_get(self) -> np.ndarray:
         out = np.empty((self.cells, 9), np.float32)
         call("pp2_fib_get", self._h, _f32(out))

@@ -13,6 +13,7 @@
 #include "pp2.h"
 #include "pp2_dict_props.h"
 #include "pp2_internal.h"
+#include "pp2_journal.h"
 
 using pp2::Geom;
 using pp2::PlaneSet;
@@ -251,6 +252,7 @@ struct pp2_ctx {
   std::vector<uint8_t> h_map;      // the map in force (unsharded contexts; else empty)
   bool model_generated = false;    // the model in force: pp2_model_generate's, kept so by updates
   unsigned model_serial = 0;       // advanced by every update that changes the model
+  pp2::ModelJournal model_journal; // ... and the rectangles each regenerated (pp2_journal.h)
   int map_incremental = 1;         // PP2_TUNE_MAP_INCREMENTAL
   long long map_updates = 0, map_patched = 0, map_rebuilds = 0;  // pp2_map_update_info
   int map_added = 0;               // dictionary rows the last update appended
@@ -300,6 +302,15 @@ int mdp_sweep_once(pp2_ctx* c);
 int build_model_dict(pp2_ctx* c);
 // model-caching objects (the planner) refuse to run once this has moved on
 inline unsigned model_serial(const pp2_ctx* c) { return c->model_serial; }
+// ... or follow it: the rectangles (clipped, non-empty) of every update newer
+// than `serial` into rects[0 .. *n), room for 2 * pp2::kJournalCap; false when
+// the journal no longer reaches back that far (refresh in full)
+inline bool model_changes_since(const pp2_ctx* c, unsigned serial, pp2::PatchRect* rects, int* n) {
+  pp2::JournalRect jr[2 * pp2::kJournalCap];
+  if (!pp2::journal_changes_since(c->model_journal, c->model_serial, serial, jr, n)) return false;
+  for (int i = 0; i < *n; ++i) rects[i] = pp2::PatchRect{jr[i].x0, jr[i].y0, jr[i].w, jr[i].h};
+  return true;
+}
 bool coded_active(const pp2_ctx* c);
 // Step pairs (k_loop_pair_coded) on this context: sparse coded model, a
 // block depth >= 2, a fitting geometry and (unless PP2_TUNE_STEP_PAIRS = 2

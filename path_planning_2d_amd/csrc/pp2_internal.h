@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pp2_journal.h"
+
 namespace pp2 {
 
 struct PlaneSet {
@@ -224,6 +226,25 @@ hipError_t launch_model_patch(hipStream_t st, const Geom& g, const uint8_t* map,
                               PatchRect r1, uint16_t* code, const float* dict,
                               const unsigned long long* tab_keys, const int* tab_vals, int* out,
                               PatchMiss* miss, int miss_cap);
+// Planner patch (pp2_map_patch.hip k_planner_patch; pp2_planner_refresh): for
+// the cells of n <= kPlannerPatchRects rectangles of the grid proper (each
+// inside it and non-empty, <= cap cells together; else hipErrorInvalidValue),
+// numbered j = 0, 1, ... rectangle by rectangle, x fastest:
+//   stage[k * cap + j]        = T plane k of the cell, k < 81
+//   stage[(81 + z) * cap + j] = L plane z, z < 16
+//   lrows[z * ld + cell] = L plane z, rrows[u * ld + cell] = R plane u, where
+//     those rows exist (null: skipped); cell = y * W + x, ld >= rows * W.
+constexpr int kPlannerPatchRects = 2 * kJournalCap;
+constexpr int kPlannerPatchCells = 4096;  // the most cells one patch takes (1.6 MB of staging)
+constexpr int kPlannerPatchT = 81, kPlannerPatchL = 16, kPlannerPatchR = 9;
+constexpr int kPlannerPatchVals = kPlannerPatchT + kPlannerPatchL + kPlannerPatchR;
+struct PlannerPatchArgs {
+  PatchRect r[kPlannerPatchRects];
+  int first[kPlannerPatchRects + 1];  // ordinal of each rectangle's first cell; [n..]: the total
+};
+hipError_t launch_planner_patch(hipStream_t st, const Geom& g, PlaneSet T, PlaneSet L, PlaneSet R,
+                                const PatchRect* rects, int n, float* stage, int cap,
+                                float* rrows, float* lrows, int ld);
 // the first n misses take their codes (< entries), each verified against its row
 hipError_t launch_patch_assign(hipStream_t st, const Geom& g, PlaneSet T, PlaneSet C, PlaneSet R,
                                PlaneSet L, const PatchMiss* miss, int n, int entries,

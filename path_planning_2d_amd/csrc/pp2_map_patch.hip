@@ -20,6 +20,16 @@
 // k_patch_assign: the host numbered the misses' new tuples, gathered their
 // rows (k_dict_gather) and now gives every missed cell its code, verified
 // bitwise against its row like any other cell.
+//
+// k_planner_patch: the planner's caches of the model (pp2_tree.cpp: hT / hL on
+// the host, the dense R and L rows on the device) follow the journalled
+// rectangles of the updates since it last read the model.  One thread per
+// (patched cell, value): blockIdx.y is the value -- T plane 0..80, L plane
+// 0..15, R plane 0..8 -- and consecutive threads take consecutive cells of a
+// rectangle, x fastest, so a wave reads runs of one plane row and writes runs
+// of one staging / dense row.  T and L go to the staging buffer as
+// [value][patched cell] (the host scatters them into the reference layouts),
+// L and R also into the dense rows at cell = y * W + x.  Plain loads and stores.
 #include "pp2_model_dev.h"
 
 namespace pp2 {
@@ -90,7 +100,68 @@ __global__ __launch_bounds__(kBlock) void k_patch_assign(Geom g, PlaneSet T, Pla
   code[cell] = (uint16_t)e;
 }
 
+__global__ __launch_bounds__(kBlock) void k_planner_patch(
+    Geom g, PlaneSet T, PlaneSet L, PlaneSet R, PlannerPatchArgs a, float* __restrict__ stage,
+    int cap, float* __restrict__ rrows, float* __restrict__ lrows, int ld) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;  // the patched cell's ordinal
+  const int v = blockIdx.y;
+  if (j >= a.first[kPlannerPatchRects] || j >= cap) return;
+  // the rectangle j falls into (constant indices: the arguments stay scalar)
+  PatchRect r = a.r[0];
+  int base = 0;
+#pragma unroll
+  for (int i = 1; i < kPlannerPatchRects; ++i)
+    if (j >= a.first[i]) {
+      r = a.r[i];
+      base = a.first[i];
+    }
+  if (r.w <= 0) return;
+  const int t = j - base;
+  const int x = r.x0 + t % r.w, y = r.y0 + t / r.w;
+  // (the host clips the rectangles; a cell off the grid proper is never touched)
+  if (x < 0 || x >= g.width || y < 0 || y >= g.rows || y >= r.y0 + r.h) return;
+  const long long cell = (long long)y * g.width + x;
+  if (v < kPlannerPatchT) {
+    stage[(long long)v * cap + j] = T.p[(long long)y * T.rs + (long long)v * T.ps + x];
+  } else if (v < kPlannerPatchT + kPlannerPatchL) {
+    const int z = v - kPlannerPatchT;
+    const float q = L.p[(long long)y * L.rs + (long long)z * L.ps + x];
+    stage[(long long)v * cap + j] = q;
+    if (lrows) lrows[(long long)z * ld + cell] = q;
+  } else if (rrows && v < kPlannerPatchVals) {
+    const int u = v - kPlannerPatchT - kPlannerPatchL;
+    rrows[(long long)u * ld + cell] = R.p[(long long)y * R.rs + (long long)u * R.ps + x];
+  }
+}
+
 }  // namespace
+
+hipError_t launch_planner_patch(hipStream_t st, const Geom& g, PlaneSet T, PlaneSet L, PlaneSet R,
+                                const PatchRect* rects, int n, float* stage, int cap,
+                                float* rrows, float* lrows, int ld) {
+  if (n < 0 || n > kPlannerPatchRects || !stage || cap <= 0) return hipErrorInvalidValue;
+  PlannerPatchArgs a;
+  int total = 0;
+  for (int i = 0; i < kPlannerPatchRects; ++i) {
+    a.r[i] = i < n ? rects[i] : PatchRect{0, 0, 0, 0};
+    a.first[i] = total;
+    if (i < n) {
+      const PatchRect& r = rects[i];
+      if (r.w <= 0 || r.h <= 0 || r.x0 < 0 || r.y0 < 0 || r.w > g.width - r.x0 ||
+          r.h > g.rows - r.y0 || (long long)total + (long long)r.w * r.h > cap)
+        return hipErrorInvalidValue;
+      total += r.w * r.h;
+    }
+  }
+  a.first[kPlannerPatchRects] = total;
+  if (total == 0) return hipSuccess;
+  if ((rrows || lrows) && (long long)ld < (long long)g.rows * g.width) return hipErrorInvalidValue;
+  // without dense rows (reference_order 0) the R values have no destination
+  const int vals = rrows ? kPlannerPatchVals : kPlannerPatchT + kPlannerPatchL;
+  hipLaunchKernelGGL(k_planner_patch, dim3((unsigned)((total + kBlock - 1) / kBlock), vals),
+                     dim3(kBlock), 0, st, g, T, L, R, a, stage, cap, rrows, lrows, ld);
+  return hipGetLastError();
+}
 
 hipError_t launch_model_patch(hipStream_t st, const Geom& g, const uint8_t* map, int gx, int gy,
                               PlaneSet T, PlaneSet L, PlaneSet R, PlaneSet C, PatchRect r0,

@@ -2119,7 +2119,11 @@ int rebuild_dict(pp2_ctx* c) {
 int model_follow(pp2_ctx* c, pp2::PatchRect r0, pp2::PatchRect r1) {
   ++c->map_updates;
   c->map_added = 0;
-  ++c->model_serial;   // planners made before this refuse to step
+  ++c->model_serial;   // planners made before this refuse to step until refreshed
+  // (valid whichever path serves the update: the full regenerate rewrites
+  // every other cell with the bits it already had)
+  c->model_journal.record(c->model_serial, pp2::JournalRect{r0.x0, r0.y0, r0.w, r0.h},
+                          pp2::JournalRect{r1.x0, r1.y0, r1.w, r1.h});
   c->res_e_dict = -1;  // as build_model_dict: whatever was decided on the old model
   ++c->agree_gen;
   break_pipeline(c);
@@ -2614,10 +2618,19 @@ int pp2_fib_sweep(pp2_ctx* c, int n) {
   return PP2_OK;
 }
 
-int pp2_fib_solve(pp2_ctx* c, int max_sweeps, int* sweeps, float* final_norm) {
+// pp2_fib_solve (warm = false: from alphas of 0) and pp2_fib_resolve (warm:
+// from the current alphas, the convergence snapshot set to them -- what
+// pp2_fib_reset leaves for alphas of 0).
+static int fib_solve_from(pp2_ctx* c, bool warm, int max_sweeps, int* sweeps, float* final_norm) {
   CHECK(check_model(c));
   DeviceGuard dg(c->device);
-  CHECK(pp2_fib_reset(c));
+  if (warm) {
+    const Planes& F = c->fib[c->fcur];
+    HIPCHK(hipMemcpyAsync(c->fibsnap.alloc, F.alloc, F.floats * sizeof(float),
+                          hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    CHECK(pp2_fib_reset(c));
+  }
   int total = 0;
   double norm = 0.0;
   do {
@@ -2629,6 +2642,14 @@ int pp2_fib_solve(pp2_ctx* c, int max_sweeps, int* sweeps, float* final_norm) {
   if (sweeps) *sweeps = total;
   if (final_norm) *final_norm = (float)norm;
   return PP2_OK;
+}
+
+int pp2_fib_solve(pp2_ctx* c, int max_sweeps, int* sweeps, float* final_norm) {
+  return fib_solve_from(c, false, max_sweeps, sweeps, final_norm);
+}
+
+int pp2_fib_resolve(pp2_ctx* c, int max_sweeps, int* sweeps, float* final_norm) {
+  return fib_solve_from(c, true, max_sweeps, sweeps, final_norm);
 }
 
 int pp2_fib_get(pp2_ctx* c, float* alphas) {

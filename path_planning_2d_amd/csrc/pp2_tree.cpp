@@ -272,6 +272,13 @@ struct pp2_planner {
   unsigned frows_version = 0;   // the context's fib_version d_frows was packed from (0: never)
   unsigned model_serial = 0;    // the context's model_serial the cached T / L (hT, hL, the
                                 // packed rows) were read at: a map or goal update moves it on
+  // pp2_planner_refresh: changed-serial refreshes, those served by the patch
+  // path and by the full one, the cells of the last refresh's patch (0: full)
+  long long refreshes = 0, refresh_patched = 0, refresh_full = 0, refresh_cells = 0;
+  // k_planner_patch's staging: [97][kPlannerPatchCells] floats of coherent
+  // pinned host memory the kernel stores into (made by the first patch)
+  float* h_stage = nullptr;
+  float* d_stage = nullptr;
   hipStream_t side = nullptr;   // reward chains beside the child chains
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_kids = nullptr;
   hipEvent_t ev_kept = nullptr;  // the kept children's rows are stored (main -> side)
@@ -1399,6 +1406,61 @@ int tree_update(pp2_planner* p, uint8_t a, uint8_t z) {
   return PP2_OK;
 }
 
+// ---------------------------------------------------------------- refresh
+// The cached model (hT / hL, the dense R and L rows) read again in full: what
+// pp2_planner_create does for them, into the buffers it made.
+int refresh_caches_full(pp2_planner* p) {
+  pp2_ctx* c = p->ctx;
+  CHECK(pp2_model_download(c, p->hT.data(), p->hL.data(), nullptr, nullptr));
+  if (p->ref) {
+    CHECK(pack_rows(p, c->R.v, 9, p->d_rrows));
+    CHECK(pack_rows(p, c->L.v, 16, p->d_lrows));
+  }
+  return PP2_OK;
+}
+
+// ... or only the cells of the journalled rectangles: one k_planner_patch
+// launch, one synchronise, the host's scatter into hT / hL.  The staging
+// buffer is host memory the kernel stores into directly (as h_out, h_belief):
+// it is written once in runs along x and read once by the host, at most 1.6 MB
+// over a 63 GB/s link, so a device buffer would only add a copy-engine
+// operation (a second queue entry and its completion signal) between the
+// kernel and the wait.
+int refresh_caches_patch(pp2_planner* p, const pp2::PatchRect* rects, int nr, int cells) {
+  pp2_ctx* c = p->ctx;
+  constexpr int cap = pp2::kPlannerPatchCells;
+  constexpr int planes = pp2::kPlannerPatchT + pp2::kPlannerPatchL;
+  if (!p->h_stage && !host_mapped((size_t)planes * cap, &p->h_stage, &p->d_stage))
+    return set_err(PP2_ENOMEM, "planner patch staging allocation failed");
+  HIPCHK(pp2::launch_planner_patch(c->stream, c->g, c->T.v, c->L.v, c->R.v, rects, nr, p->d_stage,
+                                   cap, p->ref ? p->d_rrows : nullptr,
+                                   p->ref ? p->d_lrows : nullptr, p->ref_ld));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const float* st = p->h_stage;
+  int j = 0;
+  for (int i = 0; i < nr; ++i)
+    for (int y = rects[i].y0; y < rects[i].y0 + rects[i].h; ++y)
+      for (int x = rects[i].x0; x < rects[i].x0 + rects[i].w; ++x, ++j) {
+        const size_t cell = (size_t)y * p->W + x;
+        float* t = p->hT.data() + cell * 81;
+        for (int k = 0; k < 81; ++k) t[k] = st[(size_t)k * cap + j];
+        float* l = p->hL.data() + cell * 16;
+        for (int z = 0; z < 16; ++z) l[z] = st[(size_t)(81 + z) * cap + j];
+      }
+  if (j != cells) return set_err(PP2_ESTATE, "planner patch: %d cells scattered, %d expected", j, cells);
+  return PP2_OK;
+}
+
+// Whether the context's PBVI alpha vectors still have the size the planner's
+// scratch was made for (a change is the next step's error to report).
+bool pbvi_size_stands(pp2_planner* p) {
+  if (!p->pbvi) return true;
+  const float* al = nullptr;
+  int S = 0, Sp = 0, ld = 0;
+  if (pbvi_alphas(p->ctx, &al, &S, &Sp, &ld) != PP2_OK) return false;
+  return S == p->lb_S && ld == (p->ref ? p->ref_ld : p->lb_ld);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1731,6 +1793,7 @@ int pp2_planner_destroy(pp2_planner* p) {
     if (d) (void)hipFree(d);
   if (p->h_lbv) (void)hipHostFree(p->h_lbv);
   if (p->h_out) (void)hipHostFree(p->h_out);
+  if (p->h_stage) (void)hipHostFree(p->h_stage);
   if (p->h_belief) (void)hipHostFree(p->h_belief);
   if (p->ev_belief) (void)hipEventDestroy(p->ev_belief);
   if (p->ev_done) (void)hipEventDestroy(p->ev_done);
@@ -1755,7 +1818,7 @@ int pp2_planner_step(pp2_planner* p, uint8_t action, uint8_t observation,
   pp2_ctx* c = p->ctx;
   if (p->model_serial != pp2rt::model_serial(c))
     return set_err(PP2_ESTATE, "the context's map or goal was updated after this planner was "
-                   "created (it caches the model): create a new planner");
+                   "created (it caches the model): pp2_planner_refresh it");
   DeviceGuard dg(c->device);
   if (!p->root) {
     if (!belief) return set_err(PP2_EINVAL, "first plan step needs a belief");
@@ -1798,6 +1861,88 @@ int pp2_planner_step(pp2_planner* p, uint8_t action, uint8_t observation,
     p->t_tail += std::chrono::duration<double, std::micro>(p->t_ret_step - t_loop).count();
     ++p->t_steps;
   }
+  return PP2_OK;
+}
+
+int pp2_planner_refresh(pp2_planner* p) {
+  if (!p) return set_err(PP2_EINVAL, "null planner");
+  pp2_ctx* c = p->ctx;
+  CHECK(check_model(c));
+  const unsigned now = pp2rt::model_serial(c);
+  if (p->model_serial == now) return PP2_OK;
+  DeviceGuard dg(c->device);
+  // (every expansion ends with the host's wait for both streams; the caches
+  // below are read by both)
+  HIPCHK(hipStreamSynchronize(p->side));
+  pp2::PatchRect rects[pp2::kPlannerPatchRects];
+  int nr = 0;
+  long long cells = 0;
+  bool patch = c->map_incremental != 0 && model_changes_since(c, p->model_serial, rects, &nr);
+  if (patch) {
+    for (int i = 0; i < nr; ++i) cells += (long long)rects[i].w * rects[i].h;
+    patch = cells <= pp2::kPlannerPatchCells;
+  }
+  if (patch && cells > 0) {
+    CHECK(refresh_caches_patch(p, rects, nr, (int)cells));
+  } else if (!patch) {
+    CHECK(refresh_caches_full(p));
+  }
+  p->model_serial = now;
+  ++p->refreshes;
+  ++(patch ? p->refresh_patched : p->refresh_full);
+  p->refresh_cells = patch ? cells : 0;
+  VNode* old = p->root;
+  if (!old) return PP2_OK;
+  // the tree was built under the old model: everything below the root goes,
+  // the root's belief stays in its slot and gets a fresh unexpanded root
+  for (QNode* q : old->children)
+    if (q) delete_subtree(p, q);
+  old->children.clear();
+  old->depth = 0;
+  old->vnode_to_expand = old;
+  if (old->slot < 0) return set_err(PP2_ESTATE, "root without a belief slot");
+  if (!pbvi_size_stands(p)) return PP2_OK;  // (the next step's make_root reports it)
+  const int s = old->slot;
+  VNode* nv = nullptr;
+  CHECK(make_root(p, s, old->observation, &nv));
+  old->slot = -1;  // (the slot is the new root's)
+  delete_vnode_only(p, old);
+  p->root = nv;
+  return PP2_OK;
+}
+
+int pp2_planner_refresh_info(pp2_planner* p, long long* refreshes, long long* incremental,
+                             long long* full, long long* cells_patched) {
+  if (!p) return set_err(PP2_EINVAL, "null planner");
+  if (refreshes) *refreshes = p->refreshes;
+  if (incremental) *incremental = p->refresh_patched;
+  if (full) *full = p->refresh_full;
+  if (cells_patched) *cells_patched = p->refresh_cells;
+  return PP2_OK;
+}
+
+int pp2_planner_root_belief(pp2_planner* p, float* belief) {
+  if (!p || !belief) return set_err(PP2_EINVAL, "null argument");
+  if (!p->root || p->root->slot < 0) return set_err(PP2_ESTATE, "the planner has no root");
+  pp2_ctx* c = p->ctx;
+  DeviceGuard dg(c->device);
+  const Slot& sl = p->slots[p->root->slot];
+  if (p->ref) {
+    HIPCHK(hipMemcpyAsync(belief, sl.row, p->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return PP2_OK;
+  }
+  float mass = 0.0f;
+  HIPCHK(hipMemcpyAsync(&mass, sl.mass, sizeof mass, hipMemcpyDeviceToHost, c->stream));
+  CHECK(download_planes(c, sl.b, belief, nullptr));  // (synchronises)
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < p->n; ++i) belief[i] = belief[i] / mass;
+  return PP2_OK;
+}
+
+int pp2_planner_rand_calls(pp2_planner* p, uint64_t* calls) {
+  if (!p || !calls) return set_err(PP2_EINVAL, "null argument");
+  *calls = p->rng.calls;  // (seed() zeroes it; rand_skip's draws count)
   return PP2_OK;
 }
 

@@ -99,6 +99,31 @@ class QVTreePlanner:
         call("pp2_planner_info", self._h, C.byref(t))
         return t.as_dict()
 
+    def refresh(self):
+        """Follow the context's map / goal updates (pp2_planner_refresh): the
+        cached model is patched or read again, the tree below the root goes,
+        the root keeps its belief.  Re-solve the alphas first (fib_resolve)."""
+        call("pp2_planner_refresh", self._h)
+
+    def refresh_info(self):
+        """(refreshes that found a changed model, served by the patch path, by
+        the full path, cells the last one patched)."""
+        v = [C.c_longlong() for _ in range(4)]
+        call("pp2_planner_refresh_info", self._h, *(C.byref(x) for x in v))
+        return tuple(int(x.value) for x in v)
+
+    def root_belief(self):
+        """The root's normalised belief, as a new tree would be given it."""
+        out = np.empty(self.ctx.cells, np.float32)
+        call("pp2_planner_root_belief", self._h, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
+
+    def rand_calls(self) -> int:
+        """rand_skip plus the rand() draws taken: a new planner's rand_skip."""
+        n = C.c_uint64()
+        call("pp2_planner_rand_calls", self._h, C.byref(n))
+        return int(n.value)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             from ._lib import load
