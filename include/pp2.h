@@ -757,7 +757,53 @@ int pp2_rollout_get_belief(pp2_rollout* r, int copy, float* belief);
  *     best = 0, then for u = 1..8: if (Q_best < Q_u) best = u; the control is
  *     best itself.  The vectors' own actions do not enter the choice (they are
  *     still validated <= 8).  Non-finite alpha entries are not rejected: the
- *     arithmetic above is the definition. */
+ *     arithmetic above is the definition.
+ *
+ * The world (pp2_episodes_set_world): a second context that holds the true
+ * map, while the batch's own context holds the map the robot believes.  While
+ * a world is attached, every run and every resumed segment of the batch, of
+ * all six policies and both placements, is the episode above with these
+ * changes and no other:
+ *  - initial goal test and step 6: the goal is the world's goal cell; a world
+ *    goal off the grid means there is none;
+ *  - step 2: G = G + fl(d * C_w[s][u]), C_w the world's MDP cost;
+ *    d = fl(d * gamma) uses the batch context's gamma -- the world's gamma is
+ *    never read;
+ *  - steps 3 and 4: the scans run over T_w[s][u][0..8] and L_w[s'][0..15], the
+ *    world's; uniforms, thresholds and fall-backs are unchanged;
+ *  - steps 1 and 5 are unchanged: they use the batch context's model, J, A,
+ *    Q planes, alpha sets, R planes, code plane and tables.
+ * Nothing is rejected for being inconsistent (a true cell that the believed
+ * map holds occupied, say): the arithmetic above defines the result.  The run
+ * reads the world as it stands when the run is enqueued: the launch is ordered
+ * after the work already enqueued on the world's stream, and later calls on
+ * the world context are ordered after the launch (one event in each direction
+ * when the two contexts' streams differ, nothing when they are the same);
+ * pending resident launches of the world are settled first, as the batch
+ * context's are.  The kernel reads the world's code plane and class tables
+ * from device memory, so no workgroup's LDS grows and pp2_episodes_info and
+ * every admission limit are those of a run without a world.
+ *
+ * Resumed segments (pp2_episodes_resume).  Per episode the batch keeps steps,
+ * status, cost G, the final cell, the stored belief, and the discount d.  The
+ * status is the flag for the kind of the stored belief: a status-2 episode's
+ * is the last raw update, every other one's the rescaled raw * 2^-e2 (or b0,
+ * for an episode that started on the goal), and a resumed segment never
+ * rewrites a finished episode, so a raw belief stays the raw one.  A resumed
+ * segment of `horizon` steps, for episode e:
+ *  - status != 0: nothing of the episode changes;
+ *  - else s = the final cell, b = the stored belief read as it is (it holds
+ *    raw * 2^-e2 already: no further scale), G, d and k0 = steps carry over;
+ *    the local steps j = 0 .. horizon-1 are the steps 1-6 above with global
+ *    step k = k0 + j: the uniforms are U(e, 2k) and U(e, 2k+1) with key_e made
+ *    from this call's seed; still running: steps = k0 + horizon; goal reached:
+ *    status 1, steps = k + 1; belief lost: status 2, steps = k + 1;
+ *  - the traces hold the segment only, indexed by j; the initial goal test
+ *    does not apply (k0 > 0 whenever the status is 0).
+ * So with one seed and nothing changed in between, a run of h1 steps followed
+ * by a resumed segment of h2 equals one run of h1 + h2 steps of a batch with
+ * that horizon in every result and belief bit, and the segment's trace rows
+ * are rows h1.. of the long run's. */
 typedef struct pp2_episodes pp2_episodes;
 /* episodes 1..131072, horizon 1..4096; record_trace != 0 keeps the per-step
  * trace.  PP2_ESTATE: no model, a row shard or group member, coded model
@@ -862,6 +908,33 @@ int pp2_episodes_run_lookahead_placed(pp2_episodes* ep, int alpha_set, uint64_t 
  * (PP2_ENOMEM if that fails), never at create. */
 int pp2_episodes_trace_lookahead(pp2_episodes* ep, float* q, float* rewards, float* leaf_max,
                                  int32_t* leaf_index);
+/* Attach the world ("The world" above) that every later run and resumed
+ * segment of the batch simulates; NULL detaches, which is the behaviour of a
+ * fresh batch.  world may be the batch's own context.  PP2_EINVAL: world is a
+ * row shard or group member, on another device than the batch's context, or
+ * of another height or width.  The batch keeps a plain pointer: detach, or
+ * destroy the batch, before destroying world -- the rule that holds for the
+ * batch's own context.  At every run, before any launch, world must satisfy
+ * what pp2_episodes_create demands of the batch's context except the LDS size
+ * -- a model, an active dictionary-coded model with factored rows and
+ * non-negative T and L -- else PP2_ESTATE, the message naming the world. */
+int pp2_episodes_set_world(pp2_episodes* ep, pp2_ctx* world);
+#define PP2_EPISODE_MODE 0
+#define PP2_EPISODE_QMDP 1
+#define PP2_EPISODE_FIB 2
+#define PP2_EPISODE_PBVI 3
+#define PP2_EPISODE_FIB_LOOKAHEAD 4
+#define PP2_EPISODE_PBVI_LOOKAHEAD 5
+/* Continue every episode of the batch for another `horizon` steps from the
+ * state the previous run or resumed segment left it in ("Resumed segments"
+ * above) under a PP2_EPISODE_* policy.  Follows the placement as
+ * pp2_episodes_run_lookahead_placed does and makes all the checks of the
+ * corresponding run; PP2_ESTATE before any run of the batch, PP2_EINVAL for an
+ * unknown policy.  Reads the J, A, alpha set, models and world that are
+ * current when it is enqueued: between two segments the caller may call
+ * pp2_map_update, re-solve, or attach another world.  Afterwards the results,
+ * beliefs and traces are read as after the corresponding run.  Asynchronous. */
+int pp2_episodes_resume(pp2_episodes* ep, int policy, uint64_t seed);
 
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):

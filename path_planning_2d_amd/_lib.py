@@ -142,6 +142,8 @@ SIGNATURES = {
     "pp2_episodes_run_lookahead_placed": [_vp, C.c_int, C.c_uint64, _f32p,
                                           C.POINTER(C.c_int32)],
     "pp2_episodes_trace_lookahead": [_vp, _f32p, _f32p, _f32p, C.POINTER(C.c_int32)],
+    "pp2_episodes_set_world": [_vp, _vp],
+    "pp2_episodes_resume": [_vp, C.c_int, C.c_uint64],
     "pp2_shard_group_create": [C.POINTER(_vp), C.POINTER(_vp), C.c_int],
     "pp2_shard_group_destroy": [_vp],
     "pp2_shard_group_loop_step": [_vp, C.c_uint8, C.c_uint8],

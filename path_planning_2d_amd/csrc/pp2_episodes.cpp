@@ -10,6 +10,10 @@
 // scratch allocated at the first such launch.  Every policy follows the
 // placement; the lookahead does so through pp2_episodes_run_lookahead_placed,
 // while pp2_episodes_run_lookahead keeps its contract (LDS planes or PP2_EINVAL).
+// pp2_episodes_set_world attaches a second context whose model the episodes
+// are simulated in, and pp2_episodes_resume continues every episode from the
+// batch's stored state: both launch the EXT instance of the run's policy and
+// placement (pp2_episodes.hip), a run with neither the plain one.
 #include <cstring>
 #include <vector>
 
@@ -57,6 +61,16 @@ struct pp2_episodes {
   int32_t* d_trcell = nullptr;
   int32_t* d_trmode = nullptr;
   float* d_trq = nullptr;      // [horizon][E][9]
+  // The world (pp2_episodes_set_world; null: the context's own model is the
+  // world too) and what a resumed segment continues from besides d_steps,
+  // d_status, d_cost, d_final and d_beliefs: the discounts.  An EXT launch
+  // stores them; after a plain launch they are made from d_steps when a
+  // resume needs them (disc_stale).  The events order a run against a world
+  // on another stream, one in each direction; made at the first such run.
+  pp2_ctx* world = nullptr;
+  float* d_disc = nullptr;     // [E]
+  bool disc_stale = false;
+  hipEvent_t ev_world = nullptr, ev_run = nullptr;
   std::vector<float> h_b0;     // upload staging (alive until the copies have run)
   std::vector<int32_t> h_start;
 };
@@ -83,6 +97,25 @@ int check_episode_ctx(pp2_ctx* c, const pp2_episodes* ep, long long* lds_bytes,
                    "a %d x %d belief needs %lld bytes of LDS per episode (at most %zu fit)",
                    c->g.width, c->g.rows, bytes, pp2::kDictLdsMaxBytes);
   if (lds_bytes) *lds_bytes = bytes;
+  return PP2_OK;
+}
+
+// What a run demands of the attached world, before any launch: everything
+// check_episode_ctx demands of the batch's own context but the LDS size (the
+// world's tables are read from device memory).  Settles the world's pending
+// resident launches first.
+int check_episode_world(pp2_ctx* w, const pp2_episodes* ep) {
+  CHECK(check_ctx(w));
+  if (!w->model_ready)
+    return set_err(PP2_ESTATE, "the world context has no model (not generated or uploaded)");
+  if (w->nranks > 1 || w->group || w->g.rows != w->g.grows || w->g.halo != 1)
+    return set_err(PP2_ESTATE, "the world context is sharded: episodes need an unsharded world");
+  if (!coded_active(w) || !w->dict_sparse || !w->dict_rfact || !w->dict_tl_nonneg)
+    return set_err(PP2_ESTATE,
+                   "the world context needs an active dictionary-coded model with factored rows "
+                   "(pp2_model_dict_info)");
+  if (ep->H != w->g.rows || ep->W != w->g.width || ep->wp != w->g.wp)
+    return set_err(PP2_ESTATE, "the world context's geometry is not the batch's");
   return PP2_OK;
 }
 
@@ -174,14 +207,19 @@ int global_lookahead_workgroups(const pp2_ctx* c, int episodes, int scratch_wgs)
 // by the callers).  lds_only_lookahead: pp2_episodes_run_lookahead's contract,
 // which refuses a lookahead launch that would not run from LDS planes;
 // pp2_episodes_run_lookahead_placed follows the placement as every other run.
+// resume: a resumed segment (pp2_episodes_resume; b0 and start_cells null) --
+// every episode continues from what the batch stores.
 int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const float* b0,
-             const int32_t* start_cells, bool lds_only_lookahead = false) {
+             const int32_t* start_cells, bool lds_only_lookahead = false, bool resume = false) {
   pp2_ctx* c = ep->ctx;
+  pp2_ctx* w = ep->world;
+  const bool ext = w != nullptr || resume;  // the EXT instances
   const bool look = policy == kPolicyLookahead;
   const bool alpha = policy == kPolicyAlpha || look;  // reads an alpha set
   // settles pending resident launches first: J and A below are the current ones
   long long lds = 0;
   CHECK(check_episode_ctx(c, ep, &lds, ep->placement == PP2_EPISODES_LDS));
+  if (w && w != c) CHECK(check_episode_world(w, ep));
   const int H = ep->H, W = ep->W, wp = ep->wp, E = ep->episodes;
   const size_t hw = (size_t)H * W;
   // the alpha set: the context's current one
@@ -231,13 +269,13 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
                      c->dict_n, lds);
     plan = scratch_plan(c, ep->episodes);
   }
-  for (size_t i = 0; i < hw; ++i) {
+  for (size_t i = 0; !resume && i < hw; ++i) {
     uint32_t bits;
     std::memcpy(&bits, &b0[i], 4);
     if (bits >= 0x7f800000u)  // negative (-0 too), infinite or NaN
       return set_err(PP2_EINVAL, "b0[%zu] is not finite and >= +0", i);
   }
-  for (int e = 0; e < E; ++e)
+  for (int e = 0; !resume && e < E; ++e)
     if (start_cells[e] < 0 || (size_t)start_cells[e] >= hw)
       return set_err(PP2_EINVAL, "start_cells[%d] = %d outside [0, %zu)", e, start_cells[e], hw);
   DeviceGuard dg(c->device);
@@ -291,19 +329,31 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
       if (ep->trace && !ep->d_laidx) CHECK(dev_alloc(&ep->d_laidx, HE * 144, "leaf-index trace"));
     }
   }
+  if (ext && !ep->d_disc) CHECK(dev_alloc(&ep->d_disc, (size_t)E, "discounts"));
+  const bool cross = w && w->stream != c->stream;  // the world on a stream of its own
+  if (cross && !ep->ev_world) {
+    HIPCHK(hipEventCreateWithFlags(&ep->ev_world, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ep->ev_run, hipEventDisableTiming));
+  }
   ep->lds_bytes = (int)lds;  // (a replaced model may have another dictionary size)
   ep->workgroups = global && look ? global_lookahead_workgroups(c, E, ep->scratch_wgs)
                    : global       ? ep->scratch_wgs
                    : look         ? episode_workgroups(c, E, lds, kLookaheadPerCu)
                    : alpha        ? episode_workgroups(c, E, lds)
                                   : ep->base_workgroups;
-  for (int y = 0; y < H; ++y)
-    std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
-  std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
-  HIPCHK(hipMemcpyAsync(ep->d_b0, ep->h_b0.data(), np * sizeof(float), hipMemcpyHostToDevice,
-                        c->stream));
-  HIPCHK(hipMemcpyAsync(ep->d_start, ep->h_start.data(), (size_t)E * sizeof(int32_t),
-                        hipMemcpyHostToDevice, c->stream));
+  if (!resume) {
+    for (int y = 0; y < H; ++y)
+      std::memcpy(&ep->h_b0[(size_t)y * wp], &b0[(size_t)y * W], (size_t)W * sizeof(float));
+    std::memcpy(ep->h_start.data(), start_cells, (size_t)E * sizeof(int32_t));
+    HIPCHK(hipMemcpyAsync(ep->d_b0, ep->h_b0.data(), np * sizeof(float), hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipMemcpyAsync(ep->d_start, ep->h_start.data(), (size_t)E * sizeof(int32_t),
+                          hipMemcpyHostToDevice, c->stream));
+  } else if (ep->disc_stale) {
+    // the last launch was a plain one, which stores no discounts
+    HIPCHK(pp2::launch_episode_discounts(c->stream, ep->d_steps, c->gamma, E, ep->d_disc));
+    ep->disc_stale = false;
+  }
   if (ep->trace) {
     // steps not taken: 255, 255, -1, 0, -1 (alpha runs: winner -1, its sum 0)
     HIPCHK(hipMemsetAsync(ep->d_tru, 0xff, HE, c->stream));
@@ -354,6 +404,15 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   a.seed = seed;
   a.gamma = c->gamma;
   a.goal = c->gy * W + c->gx;
+  if (w) {
+    // steps 2-4 and the goal tests are the world's; a goal off the grid is none
+    a.w_code = w->d_code;
+    a.w_rows = w->d_rows;
+    a.w_rfact = w->d_rfact;
+    a.goal = w->gx >= 0 && w->gx < W && w->gy >= 0 && w->gy < H ? w->gy * W + w->gx : -1;
+  }
+  a.resume = resume ? 1 : 0;
+  a.disc = ext ? ep->d_disc : nullptr;
   a.steps = ep->d_steps;
   a.status = ep->d_status;
   a.cost = ep->d_cost;
@@ -389,7 +448,18 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
     a.gcode = gcode;
     HIPCHK(pp2::launch_episode_pad(c->stream, c->g, c->d_code, ep->d_b0, gcode, gb0));
   }
-  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups, global));
+  // the launch reads the world as it stands behind the work already enqueued
+  // on the world's stream, and later work there waits for the launch
+  if (cross) {
+    HIPCHK(hipEventRecord(ep->ev_world, w->stream));
+    HIPCHK(hipStreamWaitEvent(c->stream, ep->ev_world, 0));
+  }
+  HIPCHK(pp2::launch_episodes(c->stream, a, policy, ep->workgroups, global, ext));
+  if (cross) {
+    HIPCHK(hipEventRecord(ep->ev_run, c->stream));
+    HIPCHK(hipStreamWaitEvent(w->stream, ep->ev_run, 0));
+  }
+  ep->disc_stale = !ext;
   ep->last_placement = global ? PP2_EPISODES_GLOBAL : PP2_EPISODES_LDS;
   ep->policy = policy;
   ep->alpha_set = alpha ? alpha_set : -1;
@@ -411,8 +481,10 @@ int pp2_episodes_destroy(pp2_episodes* ep) {
                   (void*)ep->d_trmode, (void*)ep->d_trq, (void*)ep->d_alpha,
                   (void*)ep->d_alpha_act, (void*)ep->d_trbest, (void*)ep->d_trbsum,
                   (void*)ep->d_rplanes, (void*)ep->d_larew, (void*)ep->d_lamax,
-                  (void*)ep->d_laidx, (void*)ep->d_scratch})
+                  (void*)ep->d_laidx, (void*)ep->d_scratch, (void*)ep->d_disc})
     if (p) (void)hipFree(p);
+  if (ep->ev_world) (void)hipEventDestroy(ep->ev_world);
+  if (ep->ev_run) (void)hipEventDestroy(ep->ev_run);
   delete ep;
   return PP2_OK;
 }
@@ -518,6 +590,45 @@ int pp2_episodes_run_lookahead_placed(pp2_episodes* ep, int alpha_set, uint64_t 
   if (alpha_set != PP2_ALPHA_FIB && alpha_set != PP2_ALPHA_PBVI)
     return set_err(PP2_EINVAL, "unknown alpha set %d", alpha_set);
   return run_impl(ep, kPolicyLookahead, alpha_set, seed, b0, start_cells);
+}
+
+int pp2_episodes_set_world(pp2_episodes* ep, pp2_ctx* world) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (world) {
+    pp2_ctx* c = ep->ctx;
+    if (world->nranks > 1 || world->group || world->g.rows != world->g.grows ||
+        world->g.halo != 1)
+      return set_err(PP2_EINVAL, "the world context is sharded: episodes need an unsharded world");
+    if (world->device != c->device)
+      return set_err(PP2_EINVAL, "the world context is on device %d, the batch's on device %d",
+                     world->device, c->device);
+    if (world->g.rows != ep->H || world->g.width != ep->W || world->g.wp != ep->wp)
+      return set_err(PP2_EINVAL, "the world is %d x %d, the batch %d x %d", world->g.width,
+                     world->g.rows, ep->W, ep->H);
+  }
+  ep->world = world;
+  return PP2_OK;
+}
+
+int pp2_episodes_resume(pp2_episodes* ep, int policy, uint64_t seed) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (policy < PP2_EPISODE_MODE || policy > PP2_EPISODE_PBVI_LOOKAHEAD)
+    return set_err(PP2_EINVAL, "unknown episode policy %d", policy);
+  if (ep->policy < 0) return set_err(PP2_ESTATE, "pp2_episodes_resume before any run of the batch");
+  switch (policy) {
+    case PP2_EPISODE_MODE:
+      return run_impl(ep, PP2_CONTROL_MODE, -1, seed, nullptr, nullptr, false, true);
+    case PP2_EPISODE_QMDP:
+      return run_impl(ep, PP2_CONTROL_QMDP, -1, seed, nullptr, nullptr, false, true);
+    case PP2_EPISODE_FIB:
+      return run_impl(ep, kPolicyAlpha, PP2_ALPHA_FIB, seed, nullptr, nullptr, false, true);
+    case PP2_EPISODE_PBVI:
+      return run_impl(ep, kPolicyAlpha, PP2_ALPHA_PBVI, seed, nullptr, nullptr, false, true);
+    case PP2_EPISODE_FIB_LOOKAHEAD:
+      return run_impl(ep, kPolicyLookahead, PP2_ALPHA_FIB, seed, nullptr, nullptr, false, true);
+    default:
+      return run_impl(ep, kPolicyLookahead, PP2_ALPHA_PBVI, seed, nullptr, nullptr, false, true);
+  }
 }
 
 int pp2_episodes_trace_lookahead(pp2_episodes* ep, float* q, float* rewards, float* leaf_max,

@@ -49,6 +49,24 @@
 // its launch is min(episodes, workgroups the scratch holds, CUs x 2) workgroups
 // on the first plane pairs of the same scratch (the b0 image and the code plane
 // stay behind all of the scratch's pairs, wherever they were first placed).
+//
+// The world and resumed segments (k_episodes<POLICY, GLOBAL, true>, the EXT
+// instances: a run with a world attached, or pp2_episodes_resume).  A plain run
+// launches the eight instances above, unchanged.  The EXT instances grow no LDS
+// layout -- the world's code plane, class bytes, costs, T quads, LX bytes and L
+// columns are loads at wave-uniform indices from the world context's own
+// device tables, about two dozen words a step -- and stay inside the same
+// register budgets, with no private segment, so they share the per-CU
+// constants below:
+//   VGPRs        MODE  QMDP  alpha  lookahead
+//   LDS          117   123   118    220        (plain)
+//   LDS, EXT     112   108   118    220
+//   global       121   127   118    225        (plain)
+//   global, EXT  120   114   120    229
+// A resumed episode continues from the batch's per-episode arrays: steps,
+// status, cost, final cell, the stored belief [H][wp] and the discount d
+// (EpisodeRun::disc, stored by every EXT launch; after a plain launch, which
+// stores none, launch_episode_discounts makes it from the steps).
 #pragma once
 #include "pp2_internal.h"
 
@@ -198,6 +216,18 @@ struct EpisodeRun {
   long long gstride;         // floats of a plane (ep_plane_stride)
   const float* gb0;
   const uint16_t* gcode;
+  // EXT launches only (a plain launch leaves all of these null / 0).
+  // The world (null: the batch context's model is the world too): its code
+  // plane (row 0, x 0, the geometry's row stride), factored sweep rows and
+  // class tables in device memory, read in place; goal above is then the
+  // world's goal cell, -1 if it lies off the grid.
+  const uint16_t* w_code;
+  const float* w_rows;
+  const float* w_rfact;
+  // resume != 0: continue every episode from steps / status / cost /
+  // final_cell / disc / beliefs instead of start and b0
+  int resume;
+  float* disc;               // [episodes] the discount d, stored by every EXT launch
 };
 
 // Q[u][y][x] = k_mdp_sweep's cost of action u from J (sparse coded model).
@@ -216,8 +246,15 @@ hipError_t launch_episode_alpha_planes(hipStream_t st, const Geom& g, const Plan
 // global: the global-placement instance (a.gplanes, a.gb0 and a.gcode set,
 // built by launch_episode_pad on the same stream; workgroups at most the
 // plane pairs a.gplanes holds).
+// ext: the EXT instance of the same policy and placement -- a world (a.w_*)
+// and / or a resumed segment (a.resume), a.disc set; without it both must be
+// absent, and the launch is the plain instance's.
 hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
-                           bool global = false);
+                           bool global = false, bool ext = false);
+// disc[e] = the discount after steps[e] steps (d = 1, then d = fl(d * gamma)
+// per step): what an EXT launch stores, made up after a plain run.
+hipError_t launch_episode_discounts(hipStream_t st, const int32_t* steps, float gamma,
+                                    int episodes, float* disc);
 // The padded images of a global launch: gcode[(y + 1) * ps + 4 + x] = code of
 // cell (y, x), gb0 likewise from b0 [H][wp]; everything off the grid 0.
 hipError_t launch_episode_pad(hipStream_t st, const Geom& g, const uint16_t* code,

@@ -583,7 +583,29 @@ __device__ __forceinline__ int lookahead_control(const EpisodeRun& a, const Epis
 //    that step, and the episode loop's barrier covers the final belief store.
 // The step's two __syncthreads() (and one per block of the dots, on LDS sums)
 // remain the only synchronisation.
-template <int POLICY, bool GLOBAL = false>
+//
+// EXT, the instances of a run with a world attached or of a resumed segment
+// (include/pp2.h "The world", "Resumed segments"); a plain run launches the
+// EXT = false instances, whose code the flag leaves alone.  Inside it both are
+// workgroup-uniform run-time choices:
+//  * a.w_code != null, the world: steps 2-4 take the code at s and s', the
+//    class byte of (entry, u), the cost, the T support weights, the LX byte and
+//    the sixteen L values from the world's own code plane, sweep rows and class
+//    tables in device memory -- about two dozen words a step, every lane at
+//    the same wave-uniform index (the true cell is made uniform with
+//    v_readfirstlane), so each is one L2-resident word that all workgroups
+//    share.  No LDS layout grows.  The world's codes index
+//    the world's tables only, the believed codes (sCode) the LDS tables only.
+//  * a.resume: episode e continues from its stored state -- an episode with
+//    status != 0 is left alone altogether; else s = final_cell[e], G = cost[e],
+//    d = disc[e], k0 = steps[e] and the stored belief beliefs[e] is the plane,
+//    read with sc = 1 (it holds raw * 2^-e2 already).  The LDS instance loads
+//    it where a run loads b0; the global instance copies it into the interior
+//    quads of its plane 1 (each lane its own quads, the ones step 5 stores:
+//    halo rows and x pads stay +0) and works gp1 -> gp0 -> gp1 from there.
+//    The draws and the step counts use k0 + j, the traces the local step j.
+// Every EXT launch stores the episode's discount in a.disc.
+template <int POLICY, bool GLOBAL = false, bool EXT = false>
 __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Geom g = a.g;
@@ -645,31 +667,52 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
     // never written through)
     float* cur = GLOBAL ? const_cast<float*>(a.gb0) : lds + L.b0;
     float* nxt = GLOBAL ? gp0 : lds + L.b1;
+    const bool resume = EXT && a.resume;
+    // (a finished episode of a resumed segment: nothing of it changes)
+    if (resume && a.status[e] != 0) continue;
+    // the plane an LDS workgroup starts from: b0, or the episode's stored belief
+    const float* const bsrc = resume ? a.beliefs + (long long)e * NP : a.b0;
     if constexpr (!GLOBAL) {
       for (int i = tid; i < planef; i += kEpThreads) {
         const int r = i / ps, c = i - r * ps;
         const int y = r - 1, x = c - 4;
         float v = 0.0f;
-        if (r < L.prows && y >= 0 && y < H && x >= 0 && x < wp) v = a.b0[(long long)y * wp + x];
+        if (r < L.prows && y >= 0 && y < H && x >= 0 && x < wp) v = bsrc[(long long)y * wp + x];
         cur[i] = v;
         nxt[i] = 0.0f;
       }
       __syncthreads();
+    } else if constexpr (EXT) {
+      if (resume) {
+        PP2_EP_QUADS(i0, y, x0)
+          *reinterpret_cast<f4a*>(gp1 + (y + 1) * ps + 4 + x0) =
+              *reinterpret_cast<const f4a*>(bsrc + i0);
+        cur = gp1;
+        __syncthreads();
+      }
     }
 
     const unsigned long long key = mix64(a.seed + kGolden * (unsigned long long)(e + 1));
-    const int s0 = a.start[e];
+    const int s0 = resume ? a.final_cell[e] : a.start[e];
     int sx = s0 % W, sy = s0 / W;
     float G = 0.0f, disc = 1.0f;
+    int k0 = 0;  // global step of the segment's first
+    if (resume) {
+      G = a.cost[e];
+      disc = a.disc[e];
+      k0 = a.steps[e];
+    }
     // The plane holds the last raw update; the stored belief is plane * sc,
     // sc = 2^-e2 of that update, an exact multiply (flush-to-zero) applied
     // wherever the plane is read -- the same bits as a rescaled plane, without
     // a pass over it.
     float sc = 1.0f;
-    int steps = a.horizon, status = 0;
-    if (s0 == a.goal) { steps = 0; status = 1; }
+    int steps = k0 + a.horizon, status = 0;
+    if (!resume && s0 == a.goal) { steps = 0; status = 1; }
 
+    // k: the segment's own step (the trace row), kg: the episode's
     for (int k = 0; k < a.horizon && status == 0; ++k) {
+      const int kg = k0 + k;
       // 1. control: the lane's partials
       int u = 0, mcell = 0;
       if constexpr (POLICY == 3) {
@@ -741,6 +784,55 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       u = __builtin_amdgcn_readfirstlane(u);
 
       // 2. cost, 3. motion, 4. observation: every lane, from uniform values
+      int z = 15;
+      if (EXT && a.w_code) {
+        // the world's: its device tables at wave-uniform indices (see EXT
+        // above; codes and LX bytes through their aligned dwords)
+        const float* __restrict__ const wrows = a.w_rows;
+        const float* __restrict__ const wrf = a.w_rfact;
+        const uint32_t* __restrict__ const wiw = reinterpret_cast<const uint32_t*>(wrows + kFactIW);
+        const uint32_t* __restrict__ const wlx = reinterpret_cast<const uint32_t*>(wrf + kResLX);
+        const uint32_t* __restrict__ const wcode = reinterpret_cast<const uint32_t*>(a.w_code);
+        sx = __builtin_amdgcn_readfirstlane(sx);
+        sy = __builtin_amdgcn_readfirstlane(sy);
+        const int ci = sy * wp + sx;  // (< H * wp <= INT_MAX: the planes' own index)
+        const uint32_t cs = (wcode[ci >> 1] >> (16 * (ci & 1))) & 0xffffu;
+        const uint32_t cls = ((wiw[4 * cs + (u >> 2)] >> (8 * (u & 3))) & 0xffu) >> 2;  // 4 * class
+        const float cv = wrows[kFactCT + u * kFactK * 4 + cls];
+        const float dc = disc * cv;
+        G = G + dc;
+        disc = disc * a.gamma;
+        const float r = draw(key, 2u * (unsigned)kg);
+        const float* __restrict__ const tq = wrf + kResQR + u * kFactK * 4 + cls;
+        float c = 0.0f;
+        int mv = 4;
+        bool found = false;
+        const int n = cSupN[u];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < n) {
+            const float t = tq[j];
+            c = c + t;
+            if (!found && t > 0.0f && r < c) { found = true; mv = cSup[u][j]; }
+          }
+        }
+        mv = __builtin_amdgcn_readfirstlane(mv);
+        const int nx = sx + mv % 3 - 1, ny = sy + mv / 3 - 1;
+        if (nx >= 0 && nx < W && ny >= 0 && ny < H) { sx = nx; sy = ny; }
+        const float r2 = draw(key, 2u * (unsigned)kg + 1u);
+        const int ci2 = sy * wp + sx;
+        const uint32_t cs2 = (wcode[ci2 >> 1] >> (16 * (ci2 & 1))) & 0xffffu;
+        const uint32_t lx = ((wlx[cs2 >> 2] >> (8 * (cs2 & 3))) & 0xffu) >> 2;
+        const float* __restrict__ const wlt = wrf + kResLT + lx;
+        float c2 = 0.0f;
+        bool found2 = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float l = wlt[i * kResLK];
+          c2 = c2 + l;
+          if (!found2 && l > 0.0f && r2 < c2) { found2 = true; z = i; }
+        }
+      } else {
       {
         const uint32_t cs = sCode[(sy + 1) * ps + 4 + sx];
         const uint32_t cls = sCls[u * L.epad + cs];  // 4 * class
@@ -748,7 +840,7 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
         const float dc = disc * cv;
         G = G + dc;
         disc = disc * a.gamma;
-        const float r = draw(key, 2u * (unsigned)k);
+        const float r = draw(key, 2u * (unsigned)kg);
         const float* tq = sQR + u * kFactK * 4 + cls;
         float c = 0.0f;
         int mv = 4;
@@ -766,9 +858,8 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
         // (a move off the grid is not taken: no generated model has one)
         if (nx >= 0 && nx < W && ny >= 0 && ny < H) { sx = nx; sy = ny; }
       }
-      int z = 15;
       {
-        const float r = draw(key, 2u * (unsigned)k + 1u);
+        const float r = draw(key, 2u * (unsigned)kg + 1u);
         const uint32_t lx = sLX[sCode[(sy + 1) * ps + 4 + sx]] >> 2;
         float c = 0.0f;
         bool found = false;
@@ -778,6 +869,7 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
           c = c + l;
           if (!found && l > 0.0f && r < c) { found = true; z = i; }
         }
+      }
       }
       z = __builtin_amdgcn_readfirstlane(z);
       if (a.tr_u && tid == 0) {
@@ -838,14 +930,14 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       const uint32_t mb = __float_as_uint(m);
       if (!(m > 0.0f) || mb >= 0x7f800000u) {
         status = 2;  // belief lost: the stored belief stays raw
-        steps = k + 1;
+        steps = kg + 1;
         sc = 1.0f;
       } else {
         int e2 = (int)(mb >> 23) - 127;
         e2 = e2 < -126 ? -126 : e2 > 126 ? 126 : e2;
         sc = __uint_as_float((uint32_t)(127 - e2) << 23);
         // 6. goal
-        if (sy * W + sx == a.goal) { status = 1; steps = k + 1; }
+        if (sy * W + sx == a.goal) { status = 1; steps = kg + 1; }
       }
     }
 
@@ -856,6 +948,7 @@ __global__ __launch_bounds__(kEpThreads) void k_episodes(const EpisodeRun a) {
       a.status[e] = (uint8_t)status;
       a.cost[e] = G;
       a.final_cell[e] = sy * W + sx;
+      if constexpr (EXT) a.disc[e] = disc;
     }
     float* bo = a.beliefs + (long long)e * NP;
     PP2_EP_QUADS(i0, y, x0) {
@@ -909,70 +1002,79 @@ hipError_t launch_episode_pad(hipStream_t st, const Geom& g, const uint16_t* cod
 }
 
 namespace {
-// the global placement's instances: tables, red and asum in LDS, planes in a.gplanes
-hipError_t launch_episodes_global(hipStream_t st, const EpisodeRun& a, int policy,
-                                  int workgroups) {
-  if (policy < 0 || policy > 3 || workgroups < 1 || !a.gplanes || !a.gb0 || !a.gcode ||
-      a.gstride < ((long long)a.g.rows + 2) * (a.g.wp + 4) + 4)
-    return hipErrorInvalidValue;
-  const long long bytes = episode_global_lds_bytes(a.E, policy == 3   ? ep_lookahead_floats()
-                                                        : policy == 2 ? ep_alpha_floats(a.K)
-                                                                      : 0);
-  if (bytes > (long long)kDictLdsMaxBytes) return hipErrorInvalidValue;
-  if (policy == 3) {
-    if (!a.alpha || !a.rplanes || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<3, true>), attr);
-    hipLaunchKernelGGL((k_episodes<3, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
-                       st, a);
-  } else if (policy == 2) {
-    if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<2, true>), attr);
-    hipLaunchKernelGGL((k_episodes<2, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
-                       st, a);
-  } else if (policy == 1) {
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<1, true>), attr);
-    hipLaunchKernelGGL((k_episodes<1, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
-                       st, a);
-  } else {
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<0, true>), attr);
-    hipLaunchKernelGGL((k_episodes<0, true>), dim3(workgroups), dim3(kEpThreads), (size_t)bytes,
-                       st, a);
-  }
+// One instance (16 in all: policy x placement x EXT), with its own opt-in to
+// the large LDS.
+template <int POLICY, bool GLOBAL, bool EXT>
+hipError_t launch_instance(hipStream_t st, const EpisodeRun& a, int workgroups, long long bytes) {
+  static unsigned long long attr = 0;
+  allow_lds(reinterpret_cast<const void*>(&k_episodes<POLICY, GLOBAL, EXT>), attr);
+  hipLaunchKernelGGL((k_episodes<POLICY, GLOBAL, EXT>), dim3(workgroups), dim3(kEpThreads),
+                     (size_t)bytes, st, a);
   return hipGetLastError();
+}
+template <bool GLOBAL, bool EXT>
+hipError_t launch_policy(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
+                         long long bytes) {
+  switch (policy) {
+    case 3: return launch_instance<3, GLOBAL, EXT>(st, a, workgroups, bytes);
+    case 2: return launch_instance<2, GLOBAL, EXT>(st, a, workgroups, bytes);
+    case 1: return launch_instance<1, GLOBAL, EXT>(st, a, workgroups, bytes);
+    default: return launch_instance<0, GLOBAL, EXT>(st, a, workgroups, bytes);
+  }
+}
+
+// disc[e] = the discount after steps[e] steps: d = 1, then d = fl(d * gamma)
+// once per step taken -- what an EXT launch stores itself, made up for a plain
+// run (whose instances store none) when a resumed segment follows it.
+__global__ __launch_bounds__(kBlock) void k_episode_discounts(const int32_t* __restrict__ steps,
+                                                              float gamma, int episodes,
+                                                              float* __restrict__ disc) {
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  if (e >= episodes) return;
+  float d = 1.0f;
+  for (int k = 0, n = steps[e]; k < n; ++k) d = d * gamma;
+  disc[e] = d;
 }
 }  // namespace
 
-hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
-                           bool global) {
-  if (global) return launch_episodes_global(st, a, policy, workgroups);
-  const long long bytes = policy == 3   ? episode_lookahead_lds_bytes(a.g, a.E)
-                          : policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K)
-                                        : episode_lds_bytes(a.g, a.E);
-  if (bytes > (long long)kDictLdsMaxBytes || workgroups < 1) return hipErrorInvalidValue;
-  if (policy == 3) {
-    if (!a.alpha || !a.rplanes || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<3>), attr);
-    hipLaunchKernelGGL(k_episodes<3>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
-  } else if (policy == 2) {
-    if (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax) return hipErrorInvalidValue;
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<2>), attr);
-    hipLaunchKernelGGL(k_episodes<2>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
-  } else if (policy == 1) {
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<1>), attr);
-    hipLaunchKernelGGL(k_episodes<1>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
-  } else {
-    static unsigned long long attr = 0;
-    allow_lds(reinterpret_cast<const void*>(&k_episodes<0>), attr);
-    hipLaunchKernelGGL(k_episodes<0>, dim3(workgroups), dim3(kEpThreads), (size_t)bytes, st, a);
-  }
+hipError_t launch_episode_discounts(hipStream_t st, const int32_t* steps, float gamma,
+                                    int episodes, float* disc) {
+  if (!steps || !disc || episodes < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_episode_discounts, dim3((episodes + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                     st, steps, gamma, episodes, disc);
   return hipGetLastError();
+}
+
+hipError_t launch_episodes(hipStream_t st, const EpisodeRun& a, int policy, int workgroups,
+                           bool global, bool ext) {
+  if (policy < 0 || policy > 3 || workgroups < 1) return hipErrorInvalidValue;
+  if (policy == 3 && (!a.alpha || !a.rplanes || a.K < 1 || a.K > kEpAlphaMax))
+    return hipErrorInvalidValue;
+  if (policy == 2 && (!a.alpha || !a.alpha_act || a.K < 1 || a.K > kEpAlphaMax))
+    return hipErrorInvalidValue;
+  // an EXT launch stores the discounts; a world comes with all three tables
+  if (ext && (!a.disc || (a.w_code && (!a.w_rows || !a.w_rfact)))) return hipErrorInvalidValue;
+  if (!ext && (a.resume || a.w_code)) return hipErrorInvalidValue;
+  long long bytes;
+  if (global) {
+    // tables, red and asum (the lookahead: sums and ltt) in LDS, planes in a.gplanes
+    if (!a.gplanes || !a.gb0 || !a.gcode ||
+        a.gstride < ((long long)a.g.rows + 2) * (a.g.wp + 4) + 4)
+      return hipErrorInvalidValue;
+    bytes = episode_global_lds_bytes(a.E, policy == 3   ? ep_lookahead_floats()
+                                          : policy == 2 ? ep_alpha_floats(a.K)
+                                                        : 0);
+  } else {
+    bytes = policy == 3   ? episode_lookahead_lds_bytes(a.g, a.E)
+            : policy == 2 ? episode_alpha_lds_bytes(a.g, a.E, a.K)
+                          : episode_lds_bytes(a.g, a.E);
+  }
+  if (bytes > (long long)kDictLdsMaxBytes) return hipErrorInvalidValue;
+  if (global)
+    return ext ? launch_policy<true, true>(st, a, policy, workgroups, bytes)
+               : launch_policy<true, false>(st, a, policy, workgroups, bytes);
+  return ext ? launch_policy<false, true>(st, a, policy, workgroups, bytes)
+             : launch_policy<false, false>(st, a, policy, workgroups, bytes);
 }
 
 }  // namespace pp2

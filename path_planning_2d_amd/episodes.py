@@ -35,6 +35,8 @@ EPISODES_AUTO = 2    # per launch: LDS if that launch's layout fits, else device
 _PLACEMENTS = {"lds": EPISODES_LDS, "global": EPISODES_GLOBAL, "auto": EPISODES_AUTO}
 # ``run``'s names of the one-step lookahead over a set
 _LOOKAHEAD = {"fib-lookahead": "fib", "pbvi-lookahead": "pbvi"}
+# ``resume``'s policies (PP2_EPISODE_*)
+_RESUME = {"mode": 0, "qmdp": 1, "fib": 2, "pbvi": 3, "fib-lookahead": 4, "pbvi-lookahead": 5}
 
 
 def _i32(a):
@@ -90,6 +92,7 @@ class EpisodeBatch:
         self.policy = None
         self.alpha_set = None    # of the last run, if that was an alpha or a lookahead run
         self.lookahead = False   # the last run was a lookahead run
+        self.world = None        # the attached world context (set_world)
         h = C.c_void_p()
         if placement == EPISODES_LDS:
             call("pp2_episodes_create", C.byref(h), ctx.handle, episodes, horizon,
@@ -209,6 +212,34 @@ class EpisodeBatch:
         self.policy = None
         self.alpha_set = alpha_set
         self.lookahead = True
+        return self
+
+    def set_world(self, world: GridContext | None):
+        """Attach the context that holds the true map (include/pp2.h "The
+        world"): motion, observation, cost and goal of every later ``run`` and
+        ``resume`` come from it, control and the belief update stay on the
+        batch's own context.  ``None`` detaches.  The batch keeps a reference,
+        so the world outlives it unless closed by hand."""
+        call("pp2_episodes_set_world", self._h, None if world is None else world.handle)
+        self.world = world
+        return self
+
+    def resume(self, policy, seed: int = 0):
+        """Continue every episode for another ``horizon`` steps from where the
+        last ``run`` or ``resume`` left it (include/pp2.h "Resumed segments"),
+        under ``policy``: one of the names ``run`` takes ("mode", "qmdp", "fib",
+        "pbvi", "fib-lookahead", "pbvi-lookahead").  Reads the values, alpha
+        sets, models and world current now.  Follows the placement.
+        Asynchronous."""
+        if not isinstance(policy, str) or policy not in _RESUME:
+            raise ValueError(f"unknown episode policy {policy!r}")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must fit 64 bits")
+        call("pp2_episodes_resume", self._h, _RESUME[policy], C.c_uint64(seed))
+        self.lookahead = policy in _LOOKAHEAD
+        self.alpha_set = _ALPHA_SETS.get(_LOOKAHEAD.get(policy, policy))
+        self.policy = GridContext._POLICIES[policy] if self.alpha_set is None else None
         return self
 
     def results(self) -> dict:
