@@ -936,6 +936,78 @@ int pp2_episodes_set_world(pp2_episodes* ep, pp2_ctx* world);
  * beliefs and traces are read as after the corresponding run.  Asynchronous. */
 int pp2_episodes_resume(pp2_episodes* ep, int policy, uint64_t seed);
 
+/* ---------------------------------------------------------------- shortest-path field
+ * The A* node's baseline (src/astar/path_planning_2d.cpp:109-160 of the
+ * reference: the first step of the shortest 8-connected path from the
+ * belief's mode to the goal) as a goal-rooted field over the map in force
+ * (pp2_map_get's, 1 = occupied) and the context's goal (gx, gy); it needs no
+ * model.  DESIGN.md §2.3.
+ *
+ * Move u in {0..8} \ {4} displaces by (u%3 - 1, u/3 - 1), the action raster of
+ * every other call.  Axis moves cost c_u = 1.0f, diagonal moves
+ * c_u = 0x1.6a09e6p+0f (fp32 sqrt 2, bits 0x3fb504f3).  A move is allowed iff
+ * its target cell is on the grid and free; a diagonal does not look at the two
+ * cells it passes between (the generated model's T has the same rule).
+ *   D(goal) = +0 if the goal is on the grid and free;
+ *   occupied cells hold +inf (an occupied goal too);
+ *   every other free cell x holds D(x) = min over allowed u of
+ *     fl32(D(x + off_u) + c_u), +inf where no neighbour is finite
+ *     (plain fp32 add, round to nearest, no contraction);
+ *   A_path(x): scan u = 0,1,2,3,5,6,7,8 from +inf with strict < over
+ *     fl32(D(x + off_u) + c_u), the first minimum wins; A_path = 4 at the goal,
+ *     at occupied cells and at cells with D = +inf.
+ * A goal off the grid or occupied gives all +inf and all 4: a valid, converged
+ * field with reached = 0.  fl32(a + c) > a for c >= 1 and a < 2^24, so the
+ * equations have one solution (Dijkstra's with the same add) and every
+ * relaxation order from +inf ends on the same bits; H * W <= 2^23 keeps
+ * D < 2^24 (pp2_path_solve: PP2_EINVAL above).
+ *
+ * pp2_path_solve: always starts cold; rounds of a tiled relaxation enqueued on
+ * the context's stream in batches, one synchronising poll of a pinned word per
+ * batch.  max_rounds < 1: PP2_EINVAL.  Not settled within max_rounds: PP2_OK
+ * with *converged = 0, and the field stays invalid.  rounds = the rounds up to
+ * and including the first that lowered nothing across a tile border (or
+ * max_rounds); reached = the cells with finite D (0 unless converged).  The
+ * planes are allocated at the first call (PP2_ENOMEM if that fails: the
+ * context stays usable) and freed by pp2_destroy.  A row shard, RCCL rank or
+ * group member: PP2_ESTATE.  Output pointers may be NULL.
+ *
+ * The field is valid after a converged solve until a pp2_map_update changes a
+ * cell's occupancy or a pp2_goal_set changes the goal (no warm re-solve: an
+ * added obstacle raises distances, which relaxation cannot follow).
+ * pp2_path_get, pp2_path_control and pp2_path_trace return PP2_ESTATE without
+ * a valid field.
+ *
+ * pp2_path_get: D and A_path as [H*W] arrays, either may be NULL.
+ * pp2_path_control: the A* node's beliefCallback: cell = pp2_belief_mode's,
+ * action = A_path[cell], dist = D[cell]; dist and cell may be NULL.
+ * pp2_path_trace: follows A_path from start_cell (a host copy of the table,
+ * cached per solve): cells = start ... goal inclusive, *n their count,
+ * *length = D[start].  An occupied or unreachable start: *n = 0, PP2_OK.
+ * cap < n: PP2_EINVAL with *n set to the count needed.  cells may be NULL
+ * when cap is 0; length may be NULL.
+ * pp2_path_info: whether the field is valid; rounds, kernel launches and
+ * polls of the last solve; the relaxation's tile (compile-time constants).
+ * Any pointer may be NULL. */
+int pp2_path_solve(pp2_ctx* ctx, int max_rounds, int* rounds, int* converged, int* reached);
+int pp2_path_get(pp2_ctx* ctx, float* D, uint8_t* A);
+int pp2_path_control(pp2_ctx* ctx, uint8_t* action, float* dist, int32_t* cell);
+int pp2_path_trace(pp2_ctx* ctx, int32_t start_cell, int32_t* cells, int cap, int* n,
+                   float* length);
+int pp2_path_info(pp2_ctx* ctx, int* valid, int* rounds, int* launches, int* polls,
+                  int* tile_rows, int* tile_cols);
+/* The action table step 1 of a MODE run or resumed MODE segment reads at the
+ * belief's mode: the MDP's A (the default, today's behaviour exactly) or the
+ * field's A_path of the batch's context -- in both placements, with or
+ * without a world (the table is the believed map's either way).  The setting
+ * belongs to the batch, as pp2_episodes_set_world's; every other policy
+ * ignores it, and the traces are a MODE run's.  Under PP2_TABLE_PATH a MODE
+ * run or resumed MODE segment without a valid field returns PP2_ESTATE before
+ * any launch.  An unknown table: PP2_EINVAL. */
+#define PP2_TABLE_MDP  0
+#define PP2_TABLE_PATH 1
+int pp2_episodes_set_action_table(pp2_episodes* ep, int table);
+
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):
  *  - one process per GPU: RCCL (pp2_rccl_unique_id / pp2_shard_comm_init);

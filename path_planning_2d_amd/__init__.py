@@ -8,7 +8,7 @@ package is the Python host mirror of that boundary.
 from ._lib import Pp2Error, LIB_PATH
 from .core import GridContext, ShardGroup, device_count
 from .planner import BatchedRollout, QVTreePlanner
-from .controller import BeliefMdpController
+from .controller import AStarController, BeliefMdpController
 from .episodes import (EpisodeBatch, ALPHA_FIB, ALPHA_PBVI, EPISODES_LDS, EPISODES_GLOBAL,
                        EPISODES_AUTO)
 from . import maps, synthetic
@@ -17,6 +17,7 @@ CONTROL_MODE = GridContext.CONTROL_MODE
 CONTROL_QMDP = GridContext.CONTROL_QMDP
 
 __all__ = ["GridContext", "ShardGroup", "QVTreePlanner", "BatchedRollout", "BeliefMdpController",
+           "AStarController",
            "EpisodeBatch", "CONTROL_MODE", "CONTROL_QMDP", "ALPHA_FIB", "ALPHA_PBVI", "EPISODES_LDS",
            "EPISODES_GLOBAL", "EPISODES_AUTO", "device_count",
            "Pp2Error", "LIB_PATH", "maps", "synthetic"]

@@ -144,6 +144,12 @@ SIGNATURES = {
     "pp2_episodes_trace_lookahead": [_vp, _f32p, _f32p, _f32p, C.POINTER(C.c_int32)],
     "pp2_episodes_set_world": [_vp, _vp],
     "pp2_episodes_resume": [_vp, C.c_int, C.c_uint64],
+    "pp2_path_solve": [_vp, C.c_int, _i32p, _i32p, _i32p],
+    "pp2_path_get": [_vp, _f32p, _u8p],
+    "pp2_path_control": [_vp, _u8p, _f32p, C.POINTER(C.c_int32)],
+    "pp2_path_trace": [_vp, C.c_int32, C.POINTER(C.c_int32), C.c_int, _i32p, _f32p],
+    "pp2_path_info": [_vp, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "pp2_episodes_set_action_table": [_vp, C.c_int],
     "pp2_shard_group_create": [C.POINTER(_vp), C.POINTER(_vp), C.c_int],
     "pp2_shard_group_destroy": [_vp],
     "pp2_shard_group_loop_step": [_vp, C.c_uint8, C.c_uint8],

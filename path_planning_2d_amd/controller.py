@@ -45,3 +45,25 @@ class BeliefMdpController:
         a, v, cell = self.ctx.mdp_control(self.policy)
         self.last_cell = cell
         return int(a), np.float32(v)
+
+
+class AStarController:
+    """The A* node's control over a ``GridContext`` that holds a model (for the
+    belief updates) and a valid shortest-path field (``path_solve``): every
+    message updates the belief and takes the first step of the shortest path
+    from the belief's mode (``path_control``).  ``step`` has
+    ``BeliefMdpController.step``'s shape; ``value`` is the path length from the
+    mode."""
+
+    def __init__(self, ctx: GridContext):
+        self.ctx = ctx
+        self.last_cell = -1
+
+    def step(self, action: int, observation: int, belief=None):
+        if belief is not None:
+            self.ctx.belief_set(belief)
+        else:
+            self.ctx.belief_update(action, observation)
+        a, d, cell = self.ctx.path_control()
+        self.last_cell = cell
+        return int(a), np.float32(d)

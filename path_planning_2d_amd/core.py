@@ -346,6 +346,72 @@ class GridContext:
         call("pp2_mdp_control", self._h, int(policy), C.byref(a), C.byref(v), C.byref(cell))
         return a.value, np.float32(v.value), cell.value
 
+    # ------------------------------------------------------------ shortest-path field
+    def path_solve(self, max_rounds: int | None = None):
+        """(rounds, converged, reached): the goal-rooted shortest-path field of
+        the map and goal in force, cold (pp2_path_solve).  ``max_rounds``
+        defaults to H * W.  Not converged: the field stays invalid."""
+        if max_rounds is None:
+            max_rounds = self.rows * self.width
+        r, cv, n = C.c_int(), C.c_int(), C.c_int()
+        call("pp2_path_solve", self._h, int(max_rounds), C.byref(r), C.byref(cv), C.byref(n))
+        return r.value, bool(cv.value), n.value
+
+    def path_get(self):
+        """(D[H, W] float32, A_path[H, W] uint8) of the valid field."""
+        D = np.empty((self.rows, self.width), np.float32)
+        A = np.empty((self.rows, self.width), np.uint8)
+        call("pp2_path_get", self._h, _f32(D), _u8(A))
+        return D, A
+
+    def path_control(self):
+        """(action, dist, cell): A_path and D at the belief's mode -- the A*
+        node's control, chosen on the device."""
+        a = C.c_uint8(0)
+        d = C.c_float(0.0)
+        cell = C.c_int32(0)
+        call("pp2_path_control", self._h, C.byref(a), C.byref(d), C.byref(cell))
+        return a.value, np.float32(d.value), cell.value
+
+    def path_trace(self, start):
+        """(cells int32[n], length): the path A_path walks from ``start`` (a
+        cell index y * W + x, or an (x, y) pair) to the goal, both inclusive;
+        n = 0 from an occupied or unreachable start."""
+        if isinstance(start, (tuple, list)):
+            if len(start) != 2:
+                raise ValueError("start is a cell index or an (x, y) pair")
+            x, y = int(start[0]), int(start[1])
+            if not (0 <= x < self.width and 0 <= y < self.rows):
+                raise ValueError(f"start {start!r} is off the grid")
+            cell = y * self.width + x
+        else:
+            cell = int(start)
+            if not 0 <= cell < self.rows * self.width:
+                raise ValueError(f"start cell {cell} outside [0, {self.rows * self.width})")
+        n = C.c_int(0)
+        length = C.c_float(0.0)
+        lib = _lib.load()
+        # the count first (a too-small buffer reports it), then the cells
+        st = lib.pp2_path_trace(self._h, cell, None, 0, C.byref(n), C.byref(length))
+        if st != _lib.PP2_OK and n.value == 0:
+            msg = lib.pp2_last_error()
+            raise _lib.Pp2Error(st, "pp2_path_trace", msg.decode() if msg else "")
+        cells = np.empty(n.value, np.int32)
+        if n.value:
+            call("pp2_path_trace", self._h, cell, cells.ctypes.data_as(C.POINTER(C.c_int32)),
+                 int(cells.size), C.byref(n), C.byref(length))
+        return cells, np.float32(length.value)
+
+    def path_info(self):
+        """dict: valid, and the last solve's rounds / launches / polls, and the
+        relaxation's tile (tile_rows, tile_cols)."""
+        v = [C.c_int() for _ in range(6)]
+        call("pp2_path_info", self._h, *[C.byref(x) for x in v])
+        keys = ("valid", "rounds", "launches", "polls", "tile_rows", "tile_cols")
+        out = {k: x.value for k, x in zip(keys, v)}
+        out["valid"] = bool(out["valid"])
+        return out
+
     # ------------------------------------------------------------ FIB
     def fib_reset(self):
         call("pp2_fib_reset", self._h)

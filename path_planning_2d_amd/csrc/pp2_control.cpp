@@ -73,10 +73,14 @@ int enqueue_mode(pp2_ctx* c, const ControlBufs& B) {
   return PP2_OK;
 }
 
-int finish(pp2_ctx* c, const ControlBufs& B, bool q, bool mode, uint32_t (&rec)[pp2::kControlRec]) {
+// values / table: the planes read at the mode (null: the MDP's J and A)
+int finish(pp2_ctx* c, const ControlBufs& B, bool q, bool mode, uint32_t (&rec)[pp2::kControlRec],
+           const float* values = nullptr, const uint8_t* table = nullptr) {
   const int nb = c->ctl_blocks;
   HIPCHK(pp2::launch_control_finish(c->stream, c->g, B.qpart, q ? nb : 0, c->bsum + c->bcur,
-                                    B.pv, B.pi, mode ? nb : 0, c->J[c->jcur].v.p, c->A, B.rec));
+                                    B.pv, B.pi, mode ? nb : 0,
+                                    values ? values : c->J[c->jcur].v.p, table ? table : c->A,
+                                    B.rec));
   HIPCHK(hipStreamSynchronize(c->stream));
   std::memcpy(rec, B.rec, sizeof rec);
   return PP2_OK;
@@ -147,6 +151,29 @@ int pp2_mdp_control(pp2_ctx* c, int policy, uint8_t* action, float* value, int32
     if (value) *value = word_float(rec[pp2::kControlRecModeValue]);
     if (cell) *cell = (int32_t)rec[pp2::kControlRecCell];
   }
+  return PP2_OK;
+}
+
+// The A* node's beliefCallback over the shortest-path field (pp2_path.cpp):
+// the mode and finish kernels with D and A_path in place of J and A.
+int pp2_path_control(pp2_ctx* c, uint8_t* action, float* dist, int32_t* cell) {
+  if (!c) return set_err(PP2_EINVAL, "null context");
+  if (!action) return set_err(PP2_EINVAL, "action is null");
+  CHECK(check_ctx(c));
+  CHECK(check_unsharded(c, "pp2_path_control"));
+  if (!c->path_valid)
+    return set_err(PP2_ESTATE, "pp2_path_control: no valid shortest-path field (pp2_path_solve; "
+                   "a map or goal update invalidates it)");
+  DeviceGuard dg(c->device);
+  ControlBufs B;
+  CHECK(control_bufs(c, &B));
+  CHECK(ensure_mass(c));
+  CHECK(enqueue_mode(c, B));
+  uint32_t rec[pp2::kControlRec];
+  CHECK(finish(c, B, false, true, rec, c->path_D.v.p, c->path_A));
+  *action = (uint8_t)rec[pp2::kControlRecModeAction];
+  if (dist) *dist = word_float(rec[pp2::kControlRecModeValue]);
+  if (cell) *cell = (int32_t)rec[pp2::kControlRecCell];
   return PP2_OK;
 }
 

@@ -264,6 +264,21 @@ struct pp2_ctx {
   int* d_patch_out = nullptr;                // {bad, misses}
   pp2::PatchMiss* d_miss = nullptr;          // kPatchMissCap records
   bool patch_tab_ok = false;                 // the device table matches dict_ids
+
+  // Shortest-path field (pp2_path.cpp), allocated by the first
+  // pp2_path_solve: D in a plane of J's layout, A_path in one of A's, the
+  // relaxation's device words (pp2_path.h) and the pinned record its poll
+  // kernel writes.  Valid from a converged solve until the map's occupancy or
+  // the goal changes (pp2_map_update / pp2_goal_set).
+  Planes path_D;
+  uint8_t* path_A = nullptr;
+  int* path_words = nullptr;
+  uint32_t* path_host = nullptr;
+  bool path_valid = false;
+  int path_rounds = 0, path_launches = 0, path_polls = 0;  // of the last solve
+  bool path_cached = false;        // the host copies below are the valid field's
+  std::vector<float> h_path_D;     // [H * W] (pp2_path_trace)
+  std::vector<uint8_t> h_path_A;
 };
 
 namespace pp2rt {
@@ -349,6 +364,7 @@ int read_actions(const std::string& path, std::vector<uint8_t>& v);
 std::string join(const char* dir, const char* name);
 
 void pbvi_free(pp2_ctx* c);
+void path_free(pp2_ctx* c);  // the shortest-path field's buffers (pp2_path.cpp)
 // The context's PBVI alpha vectors (device rows of ld floats, Sp rows); ESTATE if none.
 int pbvi_alphas(pp2_ctx* c, const float** alpha, int* S, int* Sp, int* ld);
 // ... and their actions (device, [S]); ESTATE if none.

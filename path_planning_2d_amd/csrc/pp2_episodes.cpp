@@ -71,6 +71,9 @@ struct pp2_episodes {
   float* d_disc = nullptr;     // [E]
   bool disc_stale = false;
   hipEvent_t ev_world = nullptr, ev_run = nullptr;
+  // The table a MODE step reads at the belief's mode
+  // (pp2_episodes_set_action_table): the MDP's A or the context's A_path.
+  int table = PP2_TABLE_MDP;
   std::vector<float> h_b0;     // upload staging (alive until the copies have run)
   std::vector<int32_t> h_start;
 };
@@ -220,6 +223,10 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   long long lds = 0;
   CHECK(check_episode_ctx(c, ep, &lds, ep->placement == PP2_EPISODES_LDS));
   if (w && w != c) CHECK(check_episode_world(w, ep));
+  const bool path_table = policy == PP2_CONTROL_MODE && ep->table == PP2_TABLE_PATH;
+  if (path_table && !c->path_valid)
+    return set_err(PP2_ESTATE, "the batch reads the shortest-path table and the context has no "
+                   "valid field (pp2_path_solve; a map or goal update invalidates it)");
   const int H = ep->H, W = ep->W, wp = ep->wp, E = ep->episodes;
   const size_t hw = (size_t)H * W;
   // the alpha set: the context's current one
@@ -390,7 +397,7 @@ int run_impl(pp2_episodes* ep, int policy, int alpha_set, uint64_t seed, const f
   a.rows = c->d_rows;
   a.rfact = c->d_rfact;
   a.Q = ep->d_q;
-  a.A = c->A;
+  a.A = path_table ? c->path_A : c->A;
   if (alpha) {
     a.alpha = ep->d_alpha;
     a.alpha_act = ep->d_alpha_act;
@@ -607,6 +614,14 @@ int pp2_episodes_set_world(pp2_episodes* ep, pp2_ctx* world) {
                      world->g.rows, ep->W, ep->H);
   }
   ep->world = world;
+  return PP2_OK;
+}
+
+int pp2_episodes_set_action_table(pp2_episodes* ep, int table) {
+  if (!ep) return set_err(PP2_EINVAL, "null episode batch");
+  if (table != PP2_TABLE_MDP && table != PP2_TABLE_PATH)
+    return set_err(PP2_EINVAL, "unknown action table %d", table);
+  ep->table = table;
   return PP2_OK;
 }
 

@@ -1775,6 +1775,7 @@ int pp2_destroy(pp2_ctx* c) {
   if (c->staging) (void)hipFree(c->staging);
   if (c->ctl_buf) (void)hipFree(c->ctl_buf);
   if (c->ctl_host) (void)hipHostFree(c->ctl_host);
+  path_free(c);
   if (c->code_alloc) (void)hipFree(c->code_alloc);
   resident_free(c);
   if (c->res_host) (void)hipHostFree(c->res_host);
@@ -2273,6 +2274,7 @@ int pp2_map_update(pp2_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
   HIPCHK(hipMemcpy2DAsync(c->d_map + (size_t)y0 * W + x0, W, &c->h_map[(size_t)y0 * W + x0], W, w,
                           h, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  if (bx1 >= 0) c->path_valid = false;  // the shortest-path field was the old map's
   if (bx1 < 0 || !c->model_ready) return PP2_OK;
   // a cell's model reads its 3x3 neighbourhood: the box dilated by one cell
   pp2::PatchRect r;
@@ -2291,6 +2293,7 @@ int pp2_goal_set(pp2_ctx* c, int32_t gx, int32_t gy) {
   if (ox == gx && oy == gy) return PP2_OK;
   c->gx = gx;
   c->gy = gy;
+  c->path_valid = false;  // the shortest-path field was the old goal's
   if (!c->model_ready) return PP2_OK;
   auto on_grid = [&](int32_t x, int32_t y) {
     return x >= 0 && x < c->g.width && y >= 0 && y < c->g.rows;

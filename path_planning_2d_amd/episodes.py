@@ -35,6 +35,8 @@ EPISODES_AUTO = 2    # per launch: LDS if that launch's layout fits, else device
 _PLACEMENTS = {"lds": EPISODES_LDS, "global": EPISODES_GLOBAL, "auto": EPISODES_AUTO}
 # ``run``'s names of the one-step lookahead over a set
 _LOOKAHEAD = {"fib-lookahead": "fib", "pbvi-lookahead": "pbvi"}
+# ``set_action_table``'s names (PP2_TABLE_*)
+_TABLES = {"mdp": 0, "path": 1}
 # ``resume``'s policies (PP2_EPISODE_*)
 _RESUME = {"mode": 0, "qmdp": 1, "fib": 2, "pbvi": 3, "fib-lookahead": 4, "pbvi-lookahead": 5}
 
@@ -222,6 +224,18 @@ class EpisodeBatch:
         so the world outlives it unless closed by hand."""
         call("pp2_episodes_set_world", self._h, None if world is None else world.handle)
         self.world = world
+        return self
+
+    def set_action_table(self, table):
+        """The table a "mode" run or resumed "mode" segment reads at the belief's
+        mode: "mdp" (the default: the MDP's action plane) or "path" (the
+        context's shortest-path table, ``GridContext.path_solve``; a run
+        without a valid field raises PP2_ESTATE).  Every other policy ignores
+        it.  Belongs to the batch, as ``set_world``."""
+        if not isinstance(table, str) or table not in _TABLES:
+            raise ValueError(f"unknown action table {table!r}")
+        call("pp2_episodes_set_action_table", self._h, _TABLES[table])
+        self.action_table = table
         return self
 
     def resume(self, policy, seed: int = 0):
