@@ -972,11 +972,34 @@ int pp2_episodes_resume(pp2_episodes* ep, int policy, uint64_t seed);
  * context stays usable) and freed by pp2_destroy.  A row shard, RCCL rank or
  * group member: PP2_ESTATE.  Output pointers may be NULL.
  *
- * The field is valid after a converged solve until a pp2_map_update changes a
- * cell's occupancy or a pp2_goal_set changes the goal (no warm re-solve: an
- * added obstacle raises distances, which relaxation cannot follow).
- * pp2_path_get, pp2_path_control and pp2_path_trace return PP2_ESTATE without
- * a valid field.
+ * The field is valid after a converged solve or resolve until a
+ * pp2_map_update changes a cell's occupancy or a pp2_goal_set changes the
+ * goal.  pp2_path_get, pp2_path_control and pp2_path_trace return PP2_ESTATE
+ * without a valid field.
+ *
+ * pp2_path_resolve: the field of the map and goal in force, the same bits as
+ * pp2_path_solve's, repaired from the converged field the planes still hold.
+ * pp2_map_update keeps the bounding box of the cells whose occupancy it
+ * changed (16 boxes at most) and pp2_goal_set notes a moved goal.  Relaxation
+ * alone cannot follow an added obstacle, because it never raises a value; so
+ * the cells of the boxes are compared with the map (seed), every value whose
+ * old A_path chain runs through a cell that is occupied now is set to +inf in
+ * raise rounds, and the relaxation's rounds repair the hole from the tiles
+ * that lost or gained a cell; then A_path and reached over the whole grid.
+ * *warm = 1 when that path served the call, 0 when the call did exactly what
+ * pp2_path_solve does: no converged field in the planes (never solved, or the
+ * last solve or resolve ended unconverged), the goal moved, the goal cell's
+ * occupancy is not what it was at field time, or more than 16 boxes pending.
+ * With a valid field it returns at once without a launch: rounds = 0,
+ * converged = 1, the stored reached, warm = 1.  The first five arguments have
+ * pp2_path_solve's contract; max_rounds bounds the raise rounds and the
+ * relaxation rounds separately, and rounds is their sum.
+ * pp2_path_resolve_info, of the last resolve: warm; raised = the cells that
+ * were finite, are still free and were raised (the newly occupied cells
+ * themselves are not counted: a function of the old field and the new map
+ * alone); the rounds of each phase (raise_rounds = 0 when no finite cell
+ * became occupied; a cold fall-back reports its rounds as relax_rounds); the
+ * cells the seed pass visited.  Any pointer may be NULL.
  *
  * pp2_path_get: D and A_path as [H*W] arrays, either may be NULL.
  * pp2_path_control: the A* node's beliefCallback: cell = pp2_belief_mode's,
@@ -987,9 +1010,13 @@ int pp2_episodes_resume(pp2_episodes* ep, int policy, uint64_t seed);
  * cap < n: PP2_EINVAL with *n set to the count needed.  cells may be NULL
  * when cap is 0; length may be NULL.
  * pp2_path_info: whether the field is valid; rounds, kernel launches and
- * polls of the last solve; the relaxation's tile (compile-time constants).
- * Any pointer may be NULL. */
+ * polls of the last solve or resolve (every kernel of the call counts); the
+ * relaxation's tile (compile-time constants).  Any pointer may be NULL. */
 int pp2_path_solve(pp2_ctx* ctx, int max_rounds, int* rounds, int* converged, int* reached);
+int pp2_path_resolve(pp2_ctx* ctx, int max_rounds, int* rounds, int* converged, int* reached,
+                     int* warm);
+int pp2_path_resolve_info(pp2_ctx* ctx, int* warm, int* raised, int* raise_rounds,
+                          int* relax_rounds, int* seed_cells);
 int pp2_path_get(pp2_ctx* ctx, float* D, uint8_t* A);
 int pp2_path_control(pp2_ctx* ctx, uint8_t* action, float* dist, int32_t* cell);
 int pp2_path_trace(pp2_ctx* ctx, int32_t start_cell, int32_t* cells, int cap, int* n,

@@ -145,6 +145,8 @@ SIGNATURES = {
     "pp2_episodes_set_world": [_vp, _vp],
     "pp2_episodes_resume": [_vp, C.c_int, C.c_uint64],
     "pp2_path_solve": [_vp, C.c_int, _i32p, _i32p, _i32p],
+    "pp2_path_resolve": [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p],
+    "pp2_path_resolve_info": [_vp, _i32p, _i32p, _i32p, _i32p, _i32p],
     "pp2_path_get": [_vp, _f32p, _u8p],
     "pp2_path_control": [_vp, _u8p, _f32p, C.POINTER(C.c_int32)],
     "pp2_path_trace": [_vp, C.c_int32, C.POINTER(C.c_int32), C.c_int, _i32p, _f32p],

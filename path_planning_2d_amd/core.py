@@ -357,6 +357,31 @@ class GridContext:
         call("pp2_path_solve", self._h, int(max_rounds), C.byref(r), C.byref(cv), C.byref(n))
         return r.value, bool(cv.value), n.value
 
+    def path_resolve(self, max_rounds: int | None = None):
+        """(rounds, converged, reached, warm): the same field as ``path_solve``,
+        repaired from the one the planes hold after ``map_update`` calls
+        (pp2_path_resolve): raise what no longer stands, then relax.  ``warm``
+        is False when the call fell back to a cold solve (no converged field,
+        the goal or its cell changed, more than 16 updates pending).  With a
+        valid field: (0, True, reached, True) without a launch."""
+        if max_rounds is None:
+            max_rounds = self.rows * self.width
+        r, cv, n, w = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        call("pp2_path_resolve", self._h, int(max_rounds), C.byref(r), C.byref(cv), C.byref(n),
+             C.byref(w))
+        return r.value, bool(cv.value), n.value, bool(w.value)
+
+    def path_resolve_info(self):
+        """dict, of the last ``path_resolve``: warm, raised (cells that were
+        finite, are still free and were raised), raise_rounds, relax_rounds,
+        seed_cells (cells of the pending rectangles the seed pass visited)."""
+        v = [C.c_int() for _ in range(5)]
+        call("pp2_path_resolve_info", self._h, *[C.byref(x) for x in v])
+        keys = ("warm", "raised", "raise_rounds", "relax_rounds", "seed_cells")
+        out = {k: x.value for k, x in zip(keys, v)}
+        out["warm"] = bool(out["warm"])
+        return out
+
     def path_get(self):
         """(D[H, W] float32, A_path[H, W] uint8) of the valid field."""
         D = np.empty((self.rows, self.width), np.float32)
@@ -403,7 +428,7 @@ class GridContext:
         return cells, np.float32(length.value)
 
     def path_info(self):
-        """dict: valid, and the last solve's rounds / launches / polls, and the
+        """dict: valid, and the last solve's or resolve's rounds / launches / polls, and the
         relaxation's tile (tile_rows, tile_cols)."""
         v = [C.c_int() for _ in range(6)]
         call("pp2_path_info", self._h, *[C.byref(x) for x in v])

@@ -14,6 +14,7 @@
 #include "pp2_dict_props.h"
 #include "pp2_internal.h"
 #include "pp2_journal.h"
+#include "pp2_path_pending.h"
 
 using pp2::Geom;
 using pp2::PlaneSet;
@@ -269,13 +270,21 @@ struct pp2_ctx {
   // pp2_path_solve: D in a plane of J's layout, A_path in one of A's, the
   // relaxation's device words (pp2_path.h) and the pinned record its poll
   // kernel writes.  Valid from a converged solve until the map's occupancy or
-  // the goal changes (pp2_map_update / pp2_goal_set).
+  // the goal changes (pp2_map_update / pp2_goal_set).  Those record what they
+  // changed in path_pending, and pp2_path_resolve repairs the field from it
+  // for as long as path_field says the planes hold a converged one.
   Planes path_D;
   uint8_t* path_A = nullptr;
   int* path_words = nullptr;
   uint32_t* path_host = nullptr;
   bool path_valid = false;
-  int path_rounds = 0, path_launches = 0, path_polls = 0;  // of the last solve
+  bool path_field = false;         // the planes hold a converged field (of the map at its time)
+  pp2::PathPending path_pending;   // changes since that field (pp2_path_pending.h)
+  int path_rounds = 0, path_launches = 0, path_polls = 0;  // of the last solve or resolve
+  int path_reached = 0;            // finite cells of the valid field
+  // of the last pp2_path_resolve (pp2_path_resolve_info)
+  int path_warm = 0, path_raised = 0, path_raise_rounds = 0, path_relax_rounds = 0;
+  int path_seed_cells = 0;
   bool path_cached = false;        // the host copies below are the valid field's
   std::vector<float> h_path_D;     // [H * W] (pp2_path_trace)
   std::vector<uint8_t> h_path_A;

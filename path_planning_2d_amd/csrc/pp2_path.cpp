@@ -6,6 +6,9 @@
 // after one synchronise (as pp2_control.cpp reads its record), so the host
 // waits once per batch and not once per round.  Rounds enqueued behind the
 // one that settled the field find no dirty tile and return at once.
+// pp2_path_resolve repairs a converged field after map updates instead of
+// starting over: a seed pass over the changed rectangles, raise rounds, then
+// the same relaxation rounds (DESIGN.md §2.3 "Warm re-solve").
 // pp2_path_control is in pp2_control.cpp, beside the kernels it reuses.
 #include <cmath>
 #include <cstring>
@@ -20,6 +23,7 @@ namespace {
 // batches: 8 rounds, doubling to kPathBatchMax (a small grid settles inside
 // the first; a long corridor pays one poll per 256 launches)
 constexpr int kFirstBatch = 8;
+static_assert(pp2::kPathSeedRects == pp2::kPathPendingCap, "the seed kernel takes the whole list");
 
 int check_path_ctx(pp2_ctx* c, const char* fn) {
   if (c->nranks > 1 || c->group || c->comm || c->g.rows != c->g.grows || c->g.halo != 1)
@@ -88,49 +92,77 @@ int cache_field(pp2_ctx* c) {
   return PP2_OK;
 }
 
-}  // namespace
-
-namespace pp2rt {
-void path_free(pp2_ctx* c) { path_release(c); }
-}  // namespace pp2rt
-
-extern "C" {
-
-int pp2_path_solve(pp2_ctx* c, int max_rounds, int* rounds, int* converged, int* reached) {
+int check_solvable(pp2_ctx* c, const char* fn, int max_rounds) {
   CHECK(check_ctx(c));
-  CHECK(check_path_ctx(c, "pp2_path_solve"));
+  CHECK(check_path_ctx(c, fn));
   if (max_rounds < 1) return set_err(PP2_EINVAL, "max_rounds = %d (at least 1)", max_rounds);
   if ((long long)c->g.rows * c->g.width > (1ll << 23))
     return set_err(PP2_EINVAL, "a %d x %d grid has more than 2^23 cells: its distances could "
                    "leave the range in which every fp32 add of a move cost is strict",
                    c->g.width, c->g.rows);
-  DeviceGuard dg(c->device);
-  CHECK(path_buffers(c));
-  c->path_valid = false;
-  c->path_cached = false;
+  return PP2_OK;
+}
+
+// the goal cell is on the grid and free in the map in force
+bool goal_free(const pp2_ctx* c) {
+  return c->gx >= 0 && c->gx < c->g.width && c->gy >= 0 && c->gy < c->g.rows &&
+         c->h_map[(size_t)c->gy * c->g.width + c->gx] != 1;
+}
+
+// A solve or resolve begins: no field until it converges, and whatever was
+// pending is its to follow.
+void begin_solve(pp2_ctx* c) {
+  c->path_valid = c->path_field = c->path_cached = false;
+  c->path_pending.clear(goal_free(c));
   c->path_rounds = c->path_launches = c->path_polls = 0;
-  float* D = c->path_D.v.p;
-  HIPCHK(pp2::launch_path_init(c->stream, c->g, c->d_map, c->gx, c->gy, D, c->path_words));
-  ++c->path_launches;
+  c->path_warm = c->path_raised = c->path_raise_rounds = c->path_relax_rounds = 0;
+  c->path_seed_cells = 0;
+}
+
+void end_solve(pp2_ctx* c, int reached) {
+  c->path_reached = reached;
+  c->path_valid = c->path_field = true;
+}
+
+// Rounds 0, 1, ... of one phase (the relaxation or the raise), enqueued in
+// batches that each end in a poll, until a round marks nobody or max_rounds
+// are done.  launch(round, slot) enqueues one round marking into marks[slot].
+template <class Launch>
+int run_rounds(pp2_ctx* c, int max_rounds, int* rounds, bool* settled, Launch launch) {
   int done = 0, batch = kFirstBatch;
-  bool settled = false;
-  while (!settled && done < max_rounds) {
+  *settled = false;
+  while (!*settled && done < max_rounds) {
     const int n = batch < max_rounds - done ? batch : max_rounds - done;
-    for (int i = 0; i < n; ++i)
-      HIPCHK(pp2::launch_path_round(c->stream, c->g, c->d_map, D, c->path_words, done + i, i));
+    for (int i = 0; i < n; ++i) HIPCHK(launch(done + i, i));
     HIPCHK(pp2::launch_path_poll(c->stream, c->path_words, n, c->path_host));
     c->path_launches += n + 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     ++c->path_polls;
     const int quiet = (int)c->path_host[pp2::kPathRecQuiet];
     if (quiet >= 0 && quiet < n) {
-      settled = true;
+      *settled = true;
       done += quiet + 1;
     } else {
       done += n;
     }
     batch = batch * 2 < pp2::kPathBatchMax ? batch * 2 : pp2::kPathBatchMax;
   }
+  *rounds = done;
+  return PP2_OK;
+}
+
+// pp2_path_solve, and pp2_path_resolve where it cannot run warm
+int solve_cold(pp2_ctx* c, int max_rounds, int* rounds, int* converged, int* reached) {
+  CHECK(path_buffers(c));
+  begin_solve(c);
+  float* D = c->path_D.v.p;
+  HIPCHK(pp2::launch_path_init(c->stream, c->g, c->d_map, c->gx, c->gy, D, c->path_words));
+  ++c->path_launches;
+  int done = 0;
+  bool settled = false;
+  CHECK(run_rounds(c, max_rounds, &done, &settled, [&](int round, int slot) {
+    return pp2::launch_path_round(c->stream, c->g, c->d_map, D, c->path_words, round, slot);
+  }));
   c->path_rounds = done;
   int cells = 0;
   if (settled) {
@@ -140,11 +172,110 @@ int pp2_path_solve(pp2_ctx* c, int max_rounds, int* rounds, int* converged, int*
     HIPCHK(hipStreamSynchronize(c->stream));
     ++c->path_polls;
     cells = (int)c->path_host[pp2::kPathRecReached];
-    c->path_valid = true;
+    end_solve(c, cells);
   }
   if (rounds) *rounds = done;
   if (converged) *converged = settled ? 1 : 0;
   if (reached) *reached = cells;
+  return PP2_OK;
+}
+
+}  // namespace
+
+namespace pp2rt {
+void path_free(pp2_ctx* c) { path_release(c); }
+}  // namespace pp2rt
+
+extern "C" {
+
+int pp2_path_solve(pp2_ctx* c, int max_rounds, int* rounds, int* converged, int* reached) {
+  CHECK(check_solvable(c, "pp2_path_solve", max_rounds));
+  DeviceGuard dg(c->device);
+  return solve_cold(c, max_rounds, rounds, converged, reached);
+}
+
+int pp2_path_resolve(pp2_ctx* c, int max_rounds, int* rounds, int* converged, int* reached,
+                     int* warm) {
+  CHECK(check_solvable(c, "pp2_path_resolve", max_rounds));
+  DeviceGuard dg(c->device);
+  if (c->path_valid) {  // nothing changed since the field: no launch
+    c->path_warm = 1;
+    c->path_raised = c->path_raise_rounds = c->path_relax_rounds = c->path_seed_cells = 0;
+    if (rounds) *rounds = 0;
+    if (converged) *converged = 1;
+    if (reached) *reached = c->path_reached;
+    if (warm) *warm = 1;
+    return PP2_OK;
+  }
+  if (!c->path_field || !c->path_pending.warm_ok(goal_free(c))) {
+    int r = 0;
+    CHECK(solve_cold(c, max_rounds, &r, converged, reached));
+    c->path_relax_rounds = r;
+    if (rounds) *rounds = r;
+    if (warm) *warm = 0;
+    return PP2_OK;
+  }
+  const pp2::PathPending pend = c->path_pending;
+  begin_solve(c);
+  c->path_warm = 1;
+  float* D = c->path_D.v.p;
+  pp2::PathSeedRects R;
+  std::memset(&R, 0, sizeof R);
+  R.n = pend.n;
+  for (int i = 0; i < pend.n; ++i) {
+    R.x0[i] = pend.r[i].x0;
+    R.y0[i] = pend.r[i].y0;
+    R.w[i] = pend.r[i].w;
+    R.h[i] = pend.r[i].h;
+  }
+  c->path_seed_cells = (int)pend.cells();
+  HIPCHK(pp2::launch_path_seed(c->stream, c->g, c->d_map, D, c->path_words, R, pend.cells()));
+  ++c->path_launches;
+  bool settled = true;
+  int raise = 0, relax = 0;
+  // no cell went from free to occupied: nothing to raise (a freed-only update
+  // costs seed + relax + actions)
+  if (pend.any_raised())
+    CHECK(run_rounds(c, max_rounds, &raise, &settled, [&](int round, int slot) {
+      return pp2::launch_path_raise_round(c->stream, c->g, c->d_map, D, c->path_A, c->path_words,
+                                          round, slot);
+    }));
+  // the relaxation starts once the raise is quiet: a stale value still
+  // standing would be copied into a raised neighbour
+  if (settled)
+    CHECK(run_rounds(c, max_rounds, &relax, &settled, [&](int round, int slot) {
+      return pp2::launch_path_round(c->stream, c->g, c->d_map, D, c->path_words, round, slot);
+    }));
+  int cells = 0;
+  if (settled) {
+    HIPCHK(pp2::launch_path_resolve_actions(c->stream, c->g, c->gx, c->gy, D, c->path_A,
+                                            c->path_words, c->path_host));
+    c->path_launches += 2;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ++c->path_polls;
+    cells = (int)c->path_host[pp2::kPathRecReached];
+    c->path_raised = (int)c->path_host[pp2::kPathRecRaised];
+    if (c->path_host[pp2::kPathRecSeeds] == 0) raise = 0;  // no finite cell became occupied
+    end_solve(c, cells);
+  }
+  c->path_rounds = raise + relax;
+  c->path_raise_rounds = raise;
+  c->path_relax_rounds = relax;
+  if (rounds) *rounds = raise + relax;
+  if (converged) *converged = settled ? 1 : 0;
+  if (reached) *reached = cells;
+  if (warm) *warm = 1;
+  return PP2_OK;
+}
+
+int pp2_path_resolve_info(pp2_ctx* c, int* warm, int* raised, int* raise_rounds,
+                          int* relax_rounds, int* seed_cells) {
+  CHECK(check_ctx(c));
+  if (warm) *warm = c->path_warm;
+  if (raised) *raised = c->path_raised;
+  if (raise_rounds) *raise_rounds = c->path_raise_rounds;
+  if (relax_rounds) *relax_rounds = c->path_relax_rounds;
+  if (seed_cells) *seed_cells = c->path_seed_cells;
   return PP2_OK;
 }
 

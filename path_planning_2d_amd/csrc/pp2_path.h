@@ -32,12 +32,27 @@ constexpr int kPathWordDirty = kPathBatchMax + 1;
 __host__ __device__ inline int path_tiles_x(const Geom& g) { return (g.width + kPathTileCols - 1) / kPathTileCols; }
 __host__ __device__ inline int path_tiles_y(const Geom& g) { return (g.rows + kPathTileRows - 1) / kPathTileRows; }
 __host__ __device__ inline int path_tiles(const Geom& g) { return path_tiles_x(g) * path_tiles_y(g); }
-inline size_t path_words(const Geom& g) { return (size_t)kPathWordDirty + 2 * (size_t)path_tiles(g); }
+// The warm re-solve's words follow: raise_dirty[2][ntiles] (the raise rounds'
+// ping-pong, as dirty[][] is the relaxation's), the count of raised cells and
+// the count of seeds (finite cells found occupied).
+__host__ __device__ inline int path_word_raise(int ntiles) { return kPathWordDirty + 2 * ntiles; }
+__host__ __device__ inline int path_word_raised(int ntiles) { return kPathWordDirty + 4 * ntiles; }
+__host__ __device__ inline int path_word_seeds(int ntiles) { return kPathWordDirty + 4 * ntiles + 1; }
+inline size_t path_words(const Geom& g) { return (size_t)kPathWordDirty + 4 * (size_t)path_tiles(g) + 2; }
 
 // The pinned record (4-byte words) the poll and report kernels write.
 constexpr int kPathRecQuiet = 0;    // index of the batch's first quiet round, -1: none
 constexpr int kPathRecReached = 1;  // cells with finite D
+constexpr int kPathRecRaised = 2;   // cells a warm re-solve raised (seeds not counted)
+constexpr int kPathRecSeeds = 3;    // finite cells its seed pass found occupied
 constexpr int kPathRec = 4;
+
+// The rectangles of a warm re-solve (pp2_path_pending.h), as a kernel argument.
+constexpr int kPathSeedRects = 16;
+struct PathSeedRects {
+  int n;
+  int x0[kPathSeedRects], y0[kPathSeedRects], w[kPathSeedRects], h[kPathSeedRects];
+};
 
 // map: the context's d_map (row stride g.width, 1 = occupied); D: the plane at
 // (row 0, x 0), rows [-1, g.rows], row stride g.wp; A: [g.rows][g.wp].
@@ -57,5 +72,22 @@ hipError_t launch_path_poll(hipStream_t st, int* words, int n, uint32_t* rec);
 // rec[kPathRecReached].
 hipError_t launch_path_actions(hipStream_t st, const Geom& g, int gx, int gy, const float* D,
                                uint8_t* A, int* words, uint32_t* rec);
+
+// Warm re-solve (DESIGN.md §2.3 "Warm re-solve"), from a converged (D, A) of
+// an earlier map and `map` as it is now.
+// Seed: every word cleared (enqueued ahead of the kernel); then one thread per
+// cell of the rectangles (on the grid, `cells` in all): an occupied cell with
+// finite D gets +inf and marks raise_dirty[0] of every tile that sees it; a
+// free cell with D = +inf marks its tile in dirty[0].
+hipError_t launch_path_seed(hipStream_t st, const Geom& g, const uint8_t* map, float* D,
+                            int* words, const PathSeedRects& rects, long long cells);
+// Round `round` of the raise: a finite cell whose parent by A reads +inf
+// becomes +inf; marks into marks[slot], raise_dirty[(round + 1) & 1] and
+// dirty[0].  A is the old field's and is only read.
+hipError_t launch_path_raise_round(hipStream_t st, const Geom& g, const uint8_t* map, float* D,
+                                   const uint8_t* A, int* words, int round, int slot);
+// launch_path_actions, reporting the raised cells and the seeds as well.
+hipError_t launch_path_resolve_actions(hipStream_t st, const Geom& g, int gx, int gy,
+                                       const float* D, uint8_t* A, int* words, uint32_t* rec);
 
 }  // namespace pp2

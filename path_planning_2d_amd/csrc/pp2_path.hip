@@ -211,6 +211,173 @@ __global__ void k_path_report(const int* __restrict__ words, uint32_t* __restric
     rec[kPathRecReached] = (uint32_t)words[kPathWordReached];
 }
 
+// ---- warm re-solve: seed, raise rounds (DESIGN.md §2.3 "Warm re-solve") ----
+//
+// The planes hold a converged (D, A) of an earlier map; `map` is the map now.
+// The seed pass compares the two on the changed rectangles; the raise rounds
+// then throw away every value whose parent chain (by the old A) runs through a
+// cell that no longer stands, and k_path_round repairs the hole.  "Parent
+// reads +inf" is a monotone operator on the set of raised cells, so as in the
+// relaxation the schedule (tile order, in-place sweeps, a ring cell read before
+// or after its owner rewrote it) changes the path taken and not the set reached.
+
+__global__ __launch_bounds__(kPathThreads) void k_path_seed(Geom g, const uint8_t* __restrict__ map,
+                                                            float* __restrict__ D,
+                                                            int* __restrict__ words,
+                                                            PathSeedRects R, long long cells) {
+  const int H = g.rows, W = g.width, wp = g.wp;
+  const int ntx = path_tiles_x(g), nty = path_tiles_y(g), nt = ntx * nty;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool in = i < cells;
+  int x = 0, y = 0;
+  if (in) {
+    int j = 0;
+    for (; j < R.n; ++j) {
+      const long long a = (long long)R.w[j] * R.h[j];
+      if (i < a) break;
+      i -= a;
+    }
+    in = j < R.n;
+    if (in) {
+      x = R.x0[j] + (int)(i % R.w[j]);
+      y = R.y0[j] + (int)(i / R.w[j]);
+      in = x >= 0 && x < W && y >= 0 && y < H;
+    }
+  }
+  bool seed = false;
+  if (in) {
+    const bool occupied = map[(long long)y * W + x] == 1;
+    const bool finite = D[(long long)y * wp + x] < INFINITY;
+    seed = occupied && finite;
+    const int ty = y / kTR, tx = x / kTC;
+    if (seed) {
+      D[(long long)y * wp + x] = INFINITY;
+      // raise-dirty: every tile that sees the seed, in its cells or in its
+      // ring (k_path_init's test for the goal)
+      int* rd = words + path_word_raise(nt);
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int ny = ty + dy, nx = tx + dx;
+          if (ny < 0 || ny >= nty || nx < 0 || nx >= ntx) continue;
+          const int y0 = ny * kTR, x0 = nx * kTC;
+          if (x >= x0 - 1 && x <= x0 + kTC && y >= y0 - 1 && y <= y0 + kTR)
+            atomicOr(&rd[ny * ntx + nx], 1);
+        }
+    } else if (!occupied && !finite) {
+      // freed, or free and unreachable before: the relaxation starts here
+      atomicOr(&words[kPathWordDirty + ty * ntx + tx], 1);
+    }
+  }
+  const unsigned long long m = __ballot(seed);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&words[path_word_seeds(nt)], (int)__popcll(m));
+}
+
+// The raise counterpart of k_path_round: the same tile, ring, LDS image and
+// lane = column layout.  A thread keeps its 8 cells' parents as LDS index
+// deltas (0: a cell that is never raised -- occupied, off the grid, the goal,
+// or +inf already, whose A is 4).  The parent read is a gather: the 64 lanes
+// of one access read row r - 1, r or r + 1 at their own column -1, 0 or +1, so
+// at most 3 lanes meet in a bank.
+__global__ __launch_bounds__(kPathThreads) void k_path_raise_round(
+    Geom g, const uint8_t* __restrict__ map, float* __restrict__ D, const uint8_t* __restrict__ A,
+    int* __restrict__ words, int round, int slot) {
+  __shared__ float sD[(kTR + 2) * kS];
+  __shared__ int s_mark;
+  const int ntx = path_tiles_x(g), nty = path_tiles_y(g), nt = ntx * nty;
+  const int tile = blockIdx.x;
+  if (tile >= nt) return;
+  int* cur = words + path_word_raise(nt) + (round & 1) * nt;
+  int* nxt = words + path_word_raise(nt) + ((round + 1) & 1) * nt;
+  if (cur[tile] == 0) return;  // (uniform over the workgroup: nobody writes cur this round)
+  const int tid = threadIdx.x;
+  const int ty = tile / ntx, tx = tile % ntx;
+  const int y0 = ty * kTR, x0 = tx * kTC;
+  const int H = g.rows, W = g.width, wp = g.wp;
+  if (tid == 0) s_mark = 0;
+  // the tile and its ring; off the grid: +inf
+  for (int i = tid; i < (kTR + 2) * kS; i += kPathThreads) {
+    const int y = y0 - 1 + i / kS, x = x0 - 1 + i % kS;
+    sD[i] = y >= 0 && y < H && x >= 0 && x < W ? D[(long long)y * wp + x] : INFINITY;
+  }
+  const int lane = tid & 63, r0 = (tid >> 6) * kRows;
+  const int x = x0 + lane;
+  int par[kRows];
+#pragma unroll
+  for (int k = 0; k < kRows; ++k) {
+    const int y = y0 + r0 + k;
+    const bool live = y < H && x < W && map[(long long)y * W + x] != 1;
+    const int u = live ? (int)A[(long long)y * wp + x] : 4;
+    par[k] = u < 9 ? (u / 3 - 1) * kS + (u % 3 - 1) : 0;
+  }
+  __syncthreads();  // (also orders every thread's read of cur[tile] before the clear below)
+  if (tid == 0) atomicAnd(&cur[tile], 0);
+  const int base = r0 * kS + lane;  // LDS index of (tile row r0 - 1, tile column lane - 1)
+  unsigned was = 0;                 // bit k: cell k was finite when the round began
+#pragma unroll
+  for (int k = 0; k < kRows; ++k)
+    was |= sD[base + (k + 1) * kS + 1] < INFINITY ? 1u << k : 0u;
+  int more = 0;
+  for (int s = 0; s < kPathInnerSweeps; ++s) {
+    int changed = 0;
+    // top-down and in place: a raise travels down a column within one sweep
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+      const int at = base + (k + 1) * kS + 1;
+      if (par[k] != 0 && sD[at] < INFINITY && !(sD[at + par[k]] < INFINITY)) {
+        sD[at] = INFINITY;
+        changed = 1;
+      }
+    }
+    more = __syncthreads_or(changed);
+    if (!more) break;
+  }
+  // +inf to what was raised; border cells among them mark the tiles that see them
+  const int rl = (H - y0 < kTR ? H - y0 : kTR) - 1, cl = (W - x0 < kTC ? W - x0 : kTC) - 1;
+  int mark = 0;  // bit (dy + 1) * 3 + (dx + 1): the tile at (ty + dy, tx + dx); bit 9: any raised
+  int count = 0;
+#pragma unroll
+  for (int k = 0; k < kRows; ++k) {
+    const int r = r0 + k;
+    const bool raised = ((was >> k) & 1u) && !(sD[base + (k + 1) * kS + 1] < INFINITY);
+    count += (int)__popcll(__ballot(raised));
+    if (!raised) continue;
+    D[(long long)(y0 + r) * wp + x] = INFINITY;
+    mark |= 1 << 9;
+    // (a one-row or one-column tile's cell is on both borders)
+    const bool up = r == 0, down = r == rl, left = lane == 0, right = lane == cl;
+    if (up) mark |= 1 << 1;
+    if (down) mark |= 1 << 7;
+    if (left) mark |= 1 << 3;
+    if (right) mark |= 1 << 5;
+    if (up && left) mark |= 1 << 0;
+    if (up && right) mark |= 1 << 2;
+    if (down && left) mark |= 1 << 6;
+    if (down && right) mark |= 1 << 8;
+  }
+  if (lane == 0 && count) atomicAdd(&words[path_word_raised(nt)], count);
+  if (more) mark |= 1 << 4;  // out of sweeps: this tile again
+  if (mark) atomicOr(&s_mark, mark);
+  __syncthreads();
+  const int all = s_mark;
+  if (tid < 9 && ((all >> tid) & 1)) {
+    const int ny = ty + tid / 3 - 1, nx = tx + tid % 3 - 1;
+    if (ny >= 0 && ny < nty && nx >= 0 && nx < ntx) {
+      atomicOr(&nxt[ny * ntx + nx], 1);
+      atomicOr(&words[kPathWordMarks + slot], 1);
+    }
+  }
+  // the relaxation's round 0 repairs what this tile lost
+  if (tid == 9 && ((all >> 9) & 1)) atomicOr(&words[kPathWordDirty + tile], 1);
+}
+
+__global__ void k_path_resolve_report(const int* __restrict__ words, int nt,
+                                      uint32_t* __restrict__ rec) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  rec[kPathRecReached] = (uint32_t)words[kPathWordReached];
+  rec[kPathRecRaised] = (uint32_t)words[path_word_raised(nt)];
+  rec[kPathRecSeeds] = (uint32_t)words[path_word_seeds(nt)];
+}
+
 }  // namespace
 
 hipError_t launch_path_init(hipStream_t st, const Geom& g, const uint8_t* map, int gx, int gy,
@@ -243,6 +410,42 @@ hipError_t launch_path_actions(hipStream_t st, const Geom& g, int gx, int gy, co
   hipLaunchKernelGGL(k_path_actions, dim3((unsigned)((n + kPathThreads - 1) / kPathThreads)),
                      dim3(kPathThreads), 0, st, g, gx, gy, D, A, words);
   hipLaunchKernelGGL(k_path_report, dim3(1), dim3(64), 0, st, words, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_path_seed(hipStream_t st, const Geom& g, const uint8_t* map, float* D,
+                            int* words, const PathSeedRects& rects, long long cells) {
+  if (rects.n < 0 || rects.n > kPathSeedRects) return hipErrorInvalidValue;
+  long long sum = 0;
+  for (int j = 0; j < rects.n; ++j) {
+    if (rects.w[j] < 1 || rects.h[j] < 1 || rects.x0[j] < 0 || rects.y0[j] < 0 ||
+        rects.w[j] > g.width - rects.x0[j] || rects.h[j] > g.rows - rects.y0[j])
+      return hipErrorInvalidValue;
+    sum += (long long)rects.w[j] * rects.h[j];
+  }
+  if (sum != cells) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(words, 0, path_words(g) * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  if (cells == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_path_seed, dim3((unsigned)((cells + kPathThreads - 1) / kPathThreads)),
+                     dim3(kPathThreads), 0, st, g, map, D, words, rects, cells);
+  return hipGetLastError();
+}
+
+hipError_t launch_path_raise_round(hipStream_t st, const Geom& g, const uint8_t* map, float* D,
+                                   const uint8_t* A, int* words, int round, int slot) {
+  if (slot < 0 || slot >= kPathBatchMax) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_path_raise_round, dim3(path_tiles(g)), dim3(kPathThreads), 0, st, g, map, D,
+                     A, words, round, slot);
+  return hipGetLastError();
+}
+
+hipError_t launch_path_resolve_actions(hipStream_t st, const Geom& g, int gx, int gy,
+                                       const float* D, uint8_t* A, int* words, uint32_t* rec) {
+  const long long n = (long long)g.rows * g.width;
+  hipLaunchKernelGGL(k_path_actions, dim3((unsigned)((n + kPathThreads - 1) / kPathThreads)),
+                     dim3(kPathThreads), 0, st, g, gx, gy, D, A, words);
+  hipLaunchKernelGGL(k_path_resolve_report, dim3(1), dim3(64), 0, st, words, path_tiles(g), rec);
   return hipGetLastError();
 }
 

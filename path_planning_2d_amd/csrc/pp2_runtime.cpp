@@ -2253,7 +2253,7 @@ int pp2_map_update(pp2_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                    h, x0, y0, W, H);
   DeviceGuard dg(c->device);
   // the stored map; the bounding box of the cells whose occupancy changes
-  bool differs = false;
+  bool differs = false, occupies = false;
   int bx0 = (int)W, bx1 = -1, by0 = (int)H, by1 = -1;
   for (uint32_t y = 0; y < h; ++y) {
     uint8_t* dst = &c->h_map[(size_t)(y0 + y) * W + x0];
@@ -2262,6 +2262,7 @@ int pp2_map_update(pp2_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
       if (dst[x] == src[x]) continue;
       differs = true;
       if ((dst[x] == 1) != (src[x] == 1)) {
+        occupies = occupies || src[x] == 1;
         bx0 = std::min(bx0, (int)(x0 + x));
         bx1 = std::max(bx1, (int)(x0 + x));
         by0 = std::min(by0, (int)(y0 + y));
@@ -2274,7 +2275,10 @@ int pp2_map_update(pp2_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
   HIPCHK(hipMemcpy2DAsync(c->d_map + (size_t)y0 * W + x0, W, &c->h_map[(size_t)y0 * W + x0], W, w,
                           h, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (bx1 >= 0) c->path_valid = false;  // the shortest-path field was the old map's
+  if (bx1 >= 0) {
+    c->path_valid = false;  // the shortest-path field was the old map's
+    c->path_pending.add(bx0, by0, bx1, by1, occupies);  // ... until pp2_path_resolve repairs it
+  }
   if (bx1 < 0 || !c->model_ready) return PP2_OK;
   // a cell's model reads its 3x3 neighbourhood: the box dilated by one cell
   pp2::PatchRect r;
@@ -2294,6 +2298,7 @@ int pp2_goal_set(pp2_ctx* c, int32_t gx, int32_t gy) {
   c->gx = gx;
   c->gy = gy;
   c->path_valid = false;  // the shortest-path field was the old goal's
+  c->path_pending.goal_moved = true;
   if (!c->model_ready) return PP2_OK;
   auto on_grid = [&](int32_t x, int32_t y) {
     return x >= 0 && x < c->g.width && y >= 0 && y < c->g.rows;
