@@ -1,6 +1,8 @@
 """Grid shapes, root beliefs and case lists of the QV-tree planner's shape
-tests, shared by test_planner_shapes_cpu.py and test_gpu_planner_shapes.py.
-Everything here is a pure function of the case.
+tests, shared by test_planner_shapes_cpu.py, test_gpu_planner_shapes.py and
+test_gpu_planner_switches.py (with planner_switch_child.py), and the table of
+the library's environment switches (SWITCHES).  Everything here is a pure
+function of the case.
 
 The planner's host side (csrc/pp2_tree.cpp) and the chain sets it launches
 (csrc/pp2_fchain.hip, csrc/pp2_pbvi_host.hip) pick kernels and scratch
@@ -210,6 +212,47 @@ def pbvi_of(H, W):
     return al, act
 
 
+TIES_ROWS = tuple(range(8, 20))
+TIES_ULP = np.float32(2.0 ** -18)  # one ulp of an fp32 in (-64, -32]
+TIES_STEPS = 3
+
+
+@functools.lru_cache(maxsize=None)
+def pbvi_ties_of(H, W):
+    """pbvi_of with rows 8 .. 19 replaced by a near-tied best group: one base
+    row with entries in [-40, -38) -- above every other row in every cell, so
+    the group holds the maximum, and still below the FIB alphas (> -34.9) --
+    moved in every cell by a seeded -3 .. 3 ulps of its own per row (exact:
+    all stay inside one binade).  The rows' true dots with a belief differ by
+    a fraction of an ulp of an entry, far less than one rounding of the fp32
+    sum, while every fp32 evaluation of a row rounds along a path of its own:
+    which row comes out highest is rounding noise, different noise for the
+    exact sequential chains and for an approximate product (PP2_PBVI_FCHAIN's
+    split-x GEMM), and the values they give differ by ulps of the sum.  (Not
+    k ulps down in every cell: fp32 products and sums are monotone, so both
+    evaluations would agree on the cell-wise highest row.)  A candidate bound
+    that is not rigorous keeps the approximate maximum's row and loses the
+    exact one (test_planner_shapes_cpu.py::test_near_tied_alphas)."""
+    n = H * W
+    al, act = pbvi_of(H, W)
+    al = al.copy()
+    rng = np.random.default_rng(77 + n)
+    lo = np.float32(-40) + TIES_STEPS * TIES_ULP
+    hi = np.float32(-38) - (TIES_STEPS + 1) * TIES_ULP
+    base = np.clip(rng.uniform(-40, -38, n).astype(np.float32), lo, hi)
+    for row in TIES_ROWS:
+        k = rng.integers(-TIES_STEPS, TIES_STEPS + 1, n).astype(np.float32)
+        al[row] = base + k * TIES_ULP
+    al.setflags(write=False)
+    return al, act
+
+
+def pbvi_alphas(H, W, sw):
+    """The PBVI alpha vectors of a case: pbvi_of, or with the switch
+    "pbvi_ties" pbvi_ties_of."""
+    return pbvi_ties_of(H, W) if sw.get("pbvi_ties") else pbvi_of(H, W)
+
+
 # ---------------------------------------------------------------- models
 def off_support_model(grid, T):
     """T with a single entry off its action's base-kernel support: the stay
@@ -236,8 +279,9 @@ ALL = [(H, W) for H, W, _ in SHAPES]
 
 # reference order (bit for bit): (H, W, belief, lower_bound_mode, following
 # steps, switches).  switches: environment variables of the planner, plus
-# "fc_walk" (pp2_debug_fc_walk's argument), "coded" (TUNE_CODED_MODEL) and
-# "off_support" (upload off_support_model).
+# "fc_walk" (pp2_debug_fc_walk's argument), "coded" (TUNE_CODED_MODEL),
+# "off_support" (upload off_support_model) and "pbvi_ties" (pbvi_ties_of for
+# pbvi_of).
 REF_CASES = []
 for _hw in ALL:
     REF_CASES.append((*_hw, "uniform", 0, 1 if _hw == LARGEST else 3, {}))
@@ -268,6 +312,181 @@ for _hw in ((33, 65), (63, 131)):
 # choice, and both sides sample from the host's sequential fp32 cdf.
 DEFAULT_CASES = [(*_hw, _kind, _lb) for _hw in ALL if _hw != LARGEST
                  for _kind in ("uniform", "delta_last") for _lb in (0, 1)]
+
+
+# ---------------------------------------------------------------- switches
+# Every environment variable the library reads (getenv("PP2_...") in
+# path_planning_2d_amd/csrc; test_planner_shapes_cpu.py::
+# test_switch_table_is_complete collects the names from the sources and holds
+# this table to them).  Per variable:
+#   default  the value that means what an unset variable means
+#   flips    the first characters the source compares against to leave the
+#            default, or "int" where it parses an integer
+#   cached   "process" (read once into a global or a function-local static:
+#            only a fresh process sees another value), "planner" (read by
+#            pp2_planner_create) or "call" (read by every launch)
+#   case     the id of a SWITCH_CASES entry that holds the non-default value
+#            to the oracle, and / or
+#   tests    existing tests that set it ("file::test", under tests/)
+#   exempt   instead of both: why no case is needed
+_SHAPES_TEST = "test_gpu_planner_shapes.py::test_reference_order_bit_exact"
+_PLANNER_TEST = "test_gpu_planner.py::test_planner_reference_order_bit_exact"
+SWITCHES = {
+    # pp2_tree.cpp, pp2_planner_create
+    "PP2_CDF_SKIP": dict(default="1", flips="0", cached="planner",
+                         tests=["test_gpu_planner.py::test_planner_cdf_zero_block_skip_exact"]),
+    "PP2_SEQ_CHAIN_MAX": dict(default=str(K["kSeqChainMax"]), flips="int", cached="planner",
+                              tests=[_SHAPES_TEST]),
+    "PP2_FX": dict(default="0", flips="1", cached="planner", tests=[_SHAPES_TEST]),
+    "PP2_FX_STAMPS": dict(default="0", flips="1", cached="planner",
+                          exempt="only allocates the fused sets' time-stamp buffer"),
+    "PP2_PBVI_FCHAIN": dict(default="0", flips="1", cached="planner",
+                            case="63x131-uniform-pbvi-2-pbvi_fchain1-pbvi_stats1"),
+    "PP2_PBVI_STATS": dict(default="0", flips="1", cached="planner",
+                           exempt="only allocates the candidate counter's host copy"),
+    "PP2_PLAN_TIMING": dict(default="0", flips="1", cached="planner",
+                            case="63x131-uniform-pbvi-2-plan_events1-plan_timing1"),
+    "PP2_PLAN_EVENTS": dict(default="0", flips="1", cached="planner",
+                            case="63x131-uniform-pbvi-2-plan_events1-plan_timing1"),
+    "PP2_SPIN_WAIT": dict(default="1", flips="0", cached="planner",
+                          case="63x131-uniform-pbvi-2-spin_wait0"),
+    "PP2_FIB_CANDS": dict(default="0", flips="1", cached="planner", tests=[_PLANNER_TEST]),
+    "PP2_FIB_UNIT": dict(default="1", flips="0", cached="planner",
+                         case="63x131-uniform-pbvi-2-fib_unit0"),
+    "PP2_HOST_JOIN": dict(default="1", flips="0", cached="planner",
+                          case="63x131-uniform-pbvi-2-host_join0"),
+    "PP2_KIDS_FIRST": dict(default="0", flips="1", cached="planner",
+                           case="63x131-uniform-pbvi-2-kids_first1"),
+    "PP2_ROW_FIRST": dict(default="0", flips="1", cached="planner", tests=[_PLANNER_TEST],
+                          case="63x131-uniform-pbvi-2-kids_first1-row_first1"),
+    # pp2_fchain.hip: globals and one function-local static
+    "PP2_FC_SUMTAB": dict(default="0", flips="1", cached="process",
+                          case="63x131-uniform-fib-2-fc_sumtab1"),
+    "PP2_FC_K9WAVE": dict(default="0", flips="1", cached="process",
+                          case="63x131-uniform-fib-2-fc_k9wave1"),
+    "PP2_FC_KEPT_GY": dict(default="0", flips="int", cached="process",
+                           case="63x131-uniform-fib-2-fc_kept_gy6"),
+    "PP2_FC_PLAN9": dict(default="0", flips="1", cached="process",
+                         case="63x131-uniform-fib-2-fc_plan91"),
+    "PP2_FC_PLAN": dict(default="1", flips="0", cached="process",
+                        case="63x131-uniform-fib-2-fc_plan0"),
+    # (covered through pp2_debug_fc_walk, which writes the cached value:
+    # REF_CASES' {"fc_walk": 0})
+    "PP2_FC_WALK": dict(default="1", flips="0", cached="process", tests=[_SHAPES_TEST]),
+    # pp2_pbvi_host.hip, every launch
+    "PP2_PAIR_DOT": dict(default="3", flips="int", cached="call",
+                         tests=["test_gpu_pbvi.py::test_evaluate_dot_shapes_bit_exact"]),
+    "PP2_PAIR_SEQ": dict(default="1", flips="0", cached="call",
+                         case="63x131-uniform-pbvi-2-pair_seq0"),
+    # (unset and "1": k_chain_walk; "2": k_chain_walk2; "0": launch_pair_seq
+    # and the sequential cdf)
+    "PP2_CHAIN_WALK": dict(default="1", flips="02", cached="call", tests=[_SHAPES_TEST],
+                           case="64x128-uniform-fib-2-chain_walk0"),
+    # pp2_kernels.hip, pp2_rollout_dev.hip, every launch
+    # (unset or empty: the kernel is chosen by the block count; "1" forces the
+    # LDS kernel, any other character the dense one)
+    "PP2_FIB_LDS": dict(default="", flips="1", cached="call",
+                        tests=["test_gpu_parity.py::test_fib_lds_equals_dense_geometries",
+                               "test_gpu_ref_pin.py::test_fib_sweeps"]),
+    "PP2_BAND_DMA16": dict(default="1", flips="0", cached="call",
+                           tests=["test_gpu_rollout_exact.py::test_rollout_exact_dma4_staging"]),
+}
+EXEMPT_ALLOWED = {"PP2_FX_STAMPS", "PP2_PBVI_STATS"}
+
+
+def differs_from_default(name, value):
+    """value leaves the default of SWITCHES[name] by what the source looks at:
+    the first character, or the parsed integer."""
+    row = SWITCHES[name]
+    if row["flips"] == "int":
+        return int(value) != int(row["default"])
+    return value[:1] in row["flips"] and value[:1] != row["default"][:1]
+
+
+# Reference-order cases of the switches no other test sets, in REF_CASES'
+# format and held the same way (planner_shape_run.run_reference_order).  The
+# shapes are the smallest of the table at which these paths still differ:
+#   63x131                    on the chain sets by the planner's own choice; 33
+#                             chunks = 9 segments with a ragged last one
+#   33x65, SEQ_CHAIN_MAX=0    9 chunks, 3 segments, W%4 n%16 n%256 ragged
+#   1x7, SEQ_CHAIN_MAX=0      one chunk, one segment, no predecessor
+#   64x128                    the last size on the walked chains (CHAIN_WALK)
+# The root expansion under the uniform belief keeps KEPT_CHILDREN of the 144
+# children (the CPU oracle; test_switch_shapes_keep_enough_children): at
+# 33x65 and 63x131 more than the kFcDevGroups = 64 groups dispatched for a
+# device group list, so its loop wraps, and with PP2_FC_KEPT_GY 1 and 6 the
+# last pass is ragged (91 % 6 = 1, 100 % 6 = 4).
+KEPT_CHILDREN = {(1, 7): 48, (33, 65): 91, (63, 131): 100}
+FC_DEV_GROUPS = 64  # pp2_fchain.hip kFcDevGroups
+_SEQ0 = {"PP2_SEQ_CHAIN_MAX": "0"}
+_CHAINS = ((63, 131, {}), (33, 65, _SEQ0))  # both on the chain sets
+
+
+def _case(H, W, lb, steps, *sws):
+    sw = {}
+    for s in sws:
+        sw.update(s)
+    return (H, W, "uniform", lb, steps, sw)
+
+
+SWITCH_CASES = []
+# read per planner or per call: set in the test's own process.  lb 1 wherever
+# the switch moves launches between the two streams or changes how they join
+# (the PBVI dots are the side stream's last and longest work)
+for _sw in ({"PP2_FIB_UNIT": "0"},
+            {"PP2_KIDS_FIRST": "1"},
+            {"PP2_KIDS_FIRST": "1", "PP2_ROW_FIRST": "1"},  # row-first wins
+            {"PP2_SPIN_WAIT": "0"},
+            {"PP2_PLAN_TIMING": "1", "PP2_PLAN_EVENTS": "1"}):
+    for _H, _W, _s in _CHAINS:
+        SWITCH_CASES.append(_case(_H, _W, 1, 2, _s, _sw))
+for _lb in (0, 1):
+    for _H, _W, _s in _CHAINS:
+        SWITCH_CASES.append(_case(_H, _W, _lb, 2, _s, {"PP2_HOST_JOIN": "0"}))
+# (PP2_PBVI_STATS=1 beside it: the candidate counter proves that a candidate
+# set ran)
+PBVI_FCHAIN = {"PP2_PBVI_FCHAIN": "1", "PP2_PBVI_STATS": "1"}
+for _H, _W, _s in ((5, 1, {}), (33, 65, {}), (33, 65, _SEQ0), (63, 131, {})):
+    SWITCH_CASES.append(_case(_H, _W, 1, 2, _s, PBVI_FCHAIN))
+# and with a near-tied best group of alphas (pbvi_ties_of), which only a
+# rigorous candidate bound survives -- the bound's radius c_rel is the
+# planner's own (pp2_tree.cpp ref_pbvi_bounds), so no kernel-level test
+# reaches it; the default leaf dots on the same alphas beside it
+TIES = {"pbvi_ties": 1}
+for _H, _W, _s in ((5, 1, {}), (33, 65, {}), (33, 65, _SEQ0), (63, 131, {})):
+    SWITCH_CASES.append(_case(_H, _W, 1, 2, _s, PBVI_FCHAIN, TIES))
+for _hw in ((33, 65), (63, 131)):
+    SWITCH_CASES.append(_case(*_hw, 1, 2, TIES))
+for _hw in ((33, 65), (63, 131)):  # n >= 1024: the variable decides
+    SWITCH_CASES.append(_case(*_hw, 1, 2, {"PP2_PAIR_SEQ": "0"}))
+for _hw in ((33, 65), (64, 128)):
+    SWITCH_CASES.append(_case(*_hw, 0, 2, {"PP2_CHAIN_WALK": "0"}))
+INPROCESS_SWITCH_CASES = list(SWITCH_CASES)
+
+# cached per process: one child process per switch set, three cases each
+CHILD_SETS = [
+    {"PP2_FC_SUMTAB": "1"},
+    {"PP2_FC_K9WAVE": "1"},
+    {"PP2_FC_K9WAVE": "1", "PP2_FIB_UNIT": "0"},
+    {"PP2_FC_PLAN9": "1"},
+    {"PP2_FC_PLAN9": "1", "PP2_FC_K9WAVE": "1"},
+    {"PP2_FC_KEPT_GY": "1"},
+    {"PP2_FC_KEPT_GY": "6"},
+    {"PP2_FC_PLAN": "0"},
+]
+
+
+def child_cases(sw):
+    return [_case(1, 7, 0, 1, _SEQ0, sw), _case(33, 65, 1, 2, _SEQ0, sw),
+            _case(63, 131, 0, 2, sw)]
+
+
+for _sw in CHILD_SETS:
+    SWITCH_CASES.extend(child_cases(_sw))
+
+
+def switch_set_id(sw):
+    return "-".join(f"{k.replace('PP2_', '').lower()}{v}" for k, v in sorted(sw.items()))
 
 
 def ref_case_id(c):

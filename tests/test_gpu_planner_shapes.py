@@ -17,10 +17,10 @@ test_gpu_parity.py) and are handed to the oracle; PBVI leaves use hand-made
 alpha vectors on both sides."""
 import ctypes as C
 
-import numpy as np
 import pytest
 
 import planner_shape_cases as PC
+from planner_shape_run import context, host_models, run_reference_order
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +28,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def host_model(oracle):
     """(T, L, R) of a table shape, generated once per shape."""
-    cache = {}
-
-    def get(H, W):
-        if (H, W) not in cache:
-            cache[(H, W)] = oracle.model_pomdp(PC.grid_of(H, W), PC.goal_of(H, W))
-        return cache[(H, W)]
-    return get
+    return host_models(oracle)
 
 
 @pytest.fixture
@@ -53,73 +47,6 @@ def fc_walk():
     yield choose
     if prev:
         f(prev[0])
-
-
-def context(P, H, W, sw, host_model):
-    """A context with its model and FIB alphas in place, and the model the
-    oracle gets: (ctx, T, L, R)."""
-    grid = PC.grid_of(H, W)
-    ctx = P.GridContext(grid, PC.goal_of(H, W), gamma=float(PC.GAMMA))
-    try:
-        ctx.model_generate()
-        T, L, R = host_model(H, W)
-        if sw.get("off_support"):
-            # one T entry outside its action's support: the coded model stays,
-            # its sparse dictionary does not (k_tree_pred<false>)
-            T, _ = PC.off_support_model(grid, T)
-            Td, Ld, Rd, Cd = ctx.model_download()
-            assert np.array_equal(Ld, L) and np.array_equal(Rd, R)
-            ctx.model_upload(T, Ld, Rd, Cd)
-            assert np.array_equal(ctx.model_download()[0].reshape(T.shape), T)
-        if "coded" in sw:
-            ctx.set_tuning(ctx.TUNE_CODED_MODEL, int(sw["coded"]))
-            assert ctx.model_dict_info()[1] == bool(sw["coded"])
-        else:
-            assert ctx.model_dict_info()[1]
-        ctx.fib_solve(max_sweeps=40)
-    except BaseException:
-        ctx.close()
-        raise
-    return ctx, T, L, R
-
-
-def run_reference_order(P, oracle, host_model, case, monkeypatch, fc_walk):
-    """One reference-order case: the device planner and the oracle in
-    lockstep, held equal at every step."""
-    H, W, kind, lb, steps, sw = case
-    for k, v in sw.items():
-        if k.startswith("PP2_"):
-            monkeypatch.setenv(k, v)
-    if "fc_walk" in sw:
-        fc_walk(sw["fc_walk"])
-    where = PC.ref_case_id(case)
-    grid = PC.grid_of(H, W)
-    b0 = PC.belief_of(H, W, kind)
-    zs = PC.zs_of(H, W, steps)
-    ctx, T, L, R = context(P, H, W, sw, host_model)
-    with ctx:
-        alphas = ctx.fib_get()
-        rpl = oracle.Planner(grid, T, L, R, alphas, max_depth=PC.MAX_DEPTH,
-                             max_iter=PC.MAX_ITER)
-        if lb:
-            pal, pact = PC.pbvi_of(H, W)
-            ctx.pbvi_set(pal, pact)
-            rpl.set_pbvi(pal, pact)
-        with P.QVTreePlanner(ctx, max_search_tree_depth=PC.MAX_DEPTH,
-                             max_online_iteration=PC.MAX_ITER, lower_bound_mode=lb,
-                             rand_skip=0, reference_order=1) as gpl:
-            a_r = 0
-            for k in range(steps + 1):
-                # both planners get the oracle's action and the seeded z
-                msg = (0, 0, b0) if k == 0 else (a_r, zs[k - 1])
-                a_g, v_g = gpl.step(*msg)
-                a_r, v_r = rpl.step(*msg)
-                gi = gpl.info()
-                PC.compare_exact(gi, rpl.info(), f"{where} step {k}")
-                assert a_g == a_r, f"{where} step {k}: action {a_g} != {a_r}"
-                assert PC.f32_bits(v_g) == PC.f32_bits(v_r), f"{where} step {k}: {v_g} != {v_r}"
-                assert gi["expansions"] > 0 and gi["total_vnodes"] > 0
-        rpl.close()
 
 
 @pytest.mark.parametrize("case", PC.REF_CASES, ids=PC.ref_case_id)

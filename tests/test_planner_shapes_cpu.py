@@ -9,7 +9,11 @@
   same action (no near-tied choice of the next node to expand exists yet);
 * the short_mass belief really runs draws off its cdf (the sampler's clamp);
 * every reference-order case small enough runs through the
-  reference-arithmetic oracle without error.
+  reference-arithmetic oracle without error;
+* the table of the library's environment switches (planner_shape_cases.
+  SWITCHES) names every variable the sources read and where each is held to
+  the oracle, and the shapes of test_gpu_planner_switches.py keep as many
+  children as its cases count on.
 """
 import functools
 import os
@@ -170,8 +174,181 @@ def test_short_mass_runs_off_the_cdf(oracle, hw):
     assert b[target] > 0
 
 
+def test_switch_table_is_complete():
+    """SWITCHES against the sources: the same names, every row held
+    somewhere that exists, every new case off its row's default."""
+    read = {}  # name -> [(file, text after the getenv)]
+    for fname in sorted(os.listdir(CSRC)):
+        if not fname.endswith((".cpp", ".hip", ".h")):
+            continue
+        with open(os.path.join(CSRC, fname)) as f:
+            text = f.read()
+        for m in re.finditer(r'getenv\(\s*"(PP2_\w+)"\s*\)', text):
+            read.setdefault(m.group(1), []).append((fname, text[m.end():m.end() + 900]))
+    assert set(read) == set(PC.SWITCHES), (
+        f"read but not in SWITCHES: {sorted(set(read) - set(PC.SWITCHES))}; "
+        f"in SWITCHES but not read: {sorted(set(PC.SWITCHES) - set(read))}")
+    assert len(PC.SWITCHES) == 25
+    ids = {PC.ref_case_id(c): c for c in PC.SWITCH_CASES}
+    assert len(ids) == len(PC.SWITCH_CASES)
+    for name, row in PC.SWITCHES.items():
+        assert row["cached"] in ("process", "planner", "call"), name
+        # the characters the row says flip it are compared in the source,
+        # after one of the variable's reads
+        after = [t for _, t in read[name]]
+        if row["flips"] == "int":
+            assert any(re.search(r"ato(i|ll)\(", t[:200]) for t in after), name
+            int(row["default"])
+        else:
+            for ch in row["flips"]:
+                assert any(f"== '{ch}'" in t for t in after), f"{name}: no == '{ch}'"
+        if "exempt" in row:
+            assert name in PC.EXEMPT_ALLOWED and row["exempt"], name
+            assert "case" not in row and "tests" not in row, name
+            continue
+        assert row.get("case") or row.get("tests"), f"{name} is held nowhere"
+        if "case" in row:
+            assert row["case"] in ids, f"{name}: no case {row['case']}"
+            sw = ids[row["case"]][5]
+            assert name in sw and PC.differs_from_default(name, sw[name]), name
+        for t in row.get("tests", []):
+            fname, test = t.split("::")
+            with open(os.path.join(ROOT, "tests", fname)) as f:
+                text = f.read()
+            assert re.search(rf"^def {test}\(", text, re.M), f"{name}: no {t}"
+            if "PC.REF_CASES" in text and name not in text:
+                # set through the case list (PP2_FC_WALK: through
+                # pp2_debug_fc_walk, which writes the cached value)
+                key = "fc_walk" if name == "PP2_FC_WALK" else name
+                assert any(key in c[5] and (key == "fc_walk" or
+                                            PC.differs_from_default(name, c[5][key]))
+                           for c in PC.REF_CASES), f"{name}: no REF_CASES entry sets it"
+            else:
+                assert name in text, f"{name} does not appear in {fname}"
+    # every variable a new case sets is set off its default, in the
+    # character (or integer) the source compares
+    for cid, c in ids.items():
+        assert c[5], cid
+        for name, value in c[5].items():
+            if name.startswith("PP2_"):
+                assert PC.differs_from_default(name, value), f"{cid}: {name}={value}"
+            else:
+                assert name == "pbvi_ties" and c[3] == 1, cid
+
+
+def test_switch_cases_cover_the_issue():
+    sw_cases = PC.SWITCH_CASES
+    assert all(c[2] == "uniform" and c[4] == (1 if (c[0], c[1]) == (1, 7) else 2)
+               for c in sw_cases)
+
+    def process_cached(sw):
+        return {k for k in sw if k in PC.SWITCHES and PC.SWITCHES[k]["cached"] == "process"}
+    # the test's own process can set every switch of an in-process case ...
+    assert all(not process_cached(c[5]) for c in PC.INPROCESS_SWITCH_CASES)
+    # ... and every child set holds one that it cannot
+    assert len(PC.CHILD_SETS) == 8 and all(process_cached(sw) for sw in PC.CHILD_SETS)
+    assert len(sw_cases) == len(PC.INPROCESS_SWITCH_CASES) + 3 * len(PC.CHILD_SETS)
+    for sw in PC.CHILD_SETS:
+        cs = PC.child_cases(sw)
+        assert [(c[0], c[1], c[3], c[4]) for c in cs] == [(1, 7, 0, 1), (33, 65, 1, 2),
+                                                          (63, 131, 0, 2)]
+        assert all(c in sw_cases and sw.items() <= c[5].items() for c in cs)
+    for H, W, _, lb, _, sw in sw_cases:
+        n = H * W
+        on_chain_sets = n > PC.K["kSeqChainMax"] or sw.get("PP2_SEQ_CHAIN_MAX") == "0"
+        if set(sw) == {"pbvi_ties"}:  # the near-tied alphas on the default leaf dots
+            assert lb == 1
+        elif "PP2_CHAIN_WALK" in sw:
+            assert n <= PC.K["kWalkMax"] and not on_chain_sets
+        elif "PP2_PAIR_SEQ" in sw:
+            assert lb == 1 and n >= 1024
+        elif "PP2_PBVI_FCHAIN" in sw:
+            assert lb == 1 and sw.get("PP2_PBVI_STATS") == "1"
+        else:  # every other switch acts on the chain sets' expansion only
+            assert on_chain_sets and PC.branches(n, W)["fc_walk"]
+            assert PC.fc_chunks(n) == {7: 1, 2145: 9, 8253: 33}[n]
+    # sumtab stays where its whole grid (segments x 144 workgroups of 256
+    # threads) is resident at once: at most 9 segments here
+    assert max(PC.fc_chunks(c[0] * c[1]) for c in sw_cases if "PP2_FC_SUMTAB" in c[5]) == 33
+    gys = sorted(int(sw["PP2_FC_KEPT_GY"]) for sw in PC.CHILD_SETS if "PP2_FC_KEPT_GY" in sw)
+    assert gys == [1, 6]
+
+
+@pytest.mark.parametrize("hw", sorted(PC.KEPT_CHILDREN), ids=PC.shape_id)
+def test_switch_shapes_keep_enough_children(oracle, hw):
+    """The kept children of the root expansion under the uniform belief: what
+    PP2_FC_KEPT_GY's loop and the 64-group dispatch cap of a device group
+    list (kFcDevGroups) run over."""
+    with open(os.path.join(CSRC, "pp2_fchain.hip")) as f:
+        found = re.findall(r"constexpr int kFcDevGroups = (\d+);", f.read())
+    assert [int(v) for v in found] == [PC.FC_DEV_GROUPS]
+    pl = oracle_planner(oracle, *hw, 0, False, PC.MAX_ITER)
+    pl.step(0, 0, PC.belief_of(*hw, "uniform"))
+    kept = int(sum(pl.info()["q_nchildren"][:9]))
+    pl.close()
+    assert kept == PC.KEPT_CHILDREN[hw]
+    gy_max = max(int(sw["PP2_FC_KEPT_GY"]) for sw in PC.CHILD_SETS if "PP2_FC_KEPT_GY" in sw)
+    assert kept > gy_max  # several children per workgroup row, several passes
+    if hw != (1, 7):
+        assert kept > PC.FC_DEV_GROUPS  # the device-list loop wraps
+        assert kept % gy_max != 0  # a ragged last pass
+
+
+@pytest.mark.parametrize("hw", sorted({(c[0], c[1]) for c in PC.SWITCH_CASES
+                                      if c[5].get("pbvi_ties")}), ids=PC.shape_id)
+def test_near_tied_alphas(hw):
+    """pbvi_ties_of: a best group that no fp32 evaluation resolves, still a
+    lower bound, the other rows untouched."""
+    n = hw[0] * hw[1]
+    al, act = PC.pbvi_ties_of(*hw)
+    al0, act0 = PC.pbvi_of(*hw)
+    ties = list(PC.TIES_ROWS)
+    rest = [i for i in range(PC.PBVI_S) if i not in ties]
+    assert np.array_equal(al[rest], al0[rest]) and np.array_equal(act, act0)
+    assert 5 in rest  # the mixed-sign row stays
+    _, _, _, alphas = host_model(*hw)
+    assert al[ties].max() < -38.0 < -34.9 < alphas.min() and al[ties].min() >= -40.0
+    # above every other row in every cell but the mixed-sign row's positive
+    # ones: the group holds the maximum for beliefs that are not concentrated
+    # on those cells (every 97th)
+    mixed = np.arange(n) % 97 == 3
+    others = [i for i in rest if i != 5]
+    assert (al[ties].min(0) > al[others].max(0)).all()
+    assert (al[ties].min(0)[~mixed] > al[5, ~mixed]).all()
+    # whole ulps apart, at most 2 * TIES_STEPS, exactly; no row of the group
+    # lies above another in every cell (fp32 sums are monotone: such a pair
+    # every evaluation would order alike)
+    steps = (al[ties] - al[ties[0]]) / PC.TIES_ULP
+    assert (steps == np.round(steps)).all() and np.abs(steps).max() <= 2 * PC.TIES_STEPS
+    if n >= 64:
+        for i in ties:
+            for j in ties:
+                assert i == j or ((al[i] < al[j]).any() and (al[i] > al[j]).any())
+    # under the uniform belief the group holds the maximum, and the true
+    # dots of its two best rows lie closer than the rounding error an fp32
+    # sum of n same-sign terms may carry ((n - 1) 2^-24 relative, each add
+    # rounding once): inside every rigorous bound on an fp32 evaluation
+    b = PC.belief_of(*hw, "uniform").astype(np.float64)
+    d = al.astype(np.float64) @ b
+    assert sorted(np.argsort(d)[::-1][:len(ties)]) == ties
+    best = np.sort(d)[::-1]
+    gap = (best[0] - best[1]) / abs(best[0])
+    assert 0 <= gap < (n - 1) * 2.0 ** -24
+
+
 SMALL_REF_CASES = [c for c in PC.REF_CASES
                    if (c[0], c[1]) not in (PC.LARGEST, PC.SECOND_LARGEST)]
+# the oracle reads no environment switch: of SWITCH_CASES (all small), each
+# schedule (shape, belief, bound, steps) that REF_CASES does not already run
+def _schedule(c):
+    return (*c[:5], bool(c[5].get("pbvi_ties")))
+
+
+_ran = {_schedule(c) for c in SMALL_REF_CASES if not c[5].get("off_support")}
+for _c in PC.SWITCH_CASES:
+    if _schedule(_c) not in _ran:
+        _ran.add(_schedule(_c))
+        SMALL_REF_CASES.append((*_c[:5], {k: v for k, v in _c[5].items() if k == "pbvi_ties"}))
 
 
 @pytest.mark.parametrize("case", SMALL_REF_CASES, ids=PC.ref_case_id)
@@ -187,7 +364,7 @@ def test_reference_oracle_runs_the_schedule(oracle, case):
         assert T[cell, 4].sum() == 1.0
     pl = oracle.Planner(grid, T, L, R, alphas, max_depth=PC.MAX_DEPTH, max_iter=PC.MAX_ITER)
     if lb:
-        pl.set_pbvi(*PC.pbvi_of(H, W))
+        pl.set_pbvi(*PC.pbvi_alphas(H, W, sw))
     a, v = pl.step(0, 0, PC.belief_of(H, W, kind))
     zs = PC.zs_of(H, W, steps)
     for k in range(steps + 1):
