@@ -84,11 +84,24 @@ int pp2_get_geometry(pp2_ctx* ctx, uint32_t* rows, uint32_t* width,
                      uint32_t* row_stride, uint32_t* row_begin);
 /* Tuning: cells per lane of the streaming kernels (1, 2 or 4; default 4). */
 int pp2_set_cells_per_lane(pp2_ctx* ctx, int cpt);
-/* Tuning knobs (results are identical for every setting):
- *  PP2_TUNE_CELLS_PER_LANE  1, 2 or 4
+/* Tuning knobs.  Unless a key says otherwise, values, actions, the raw
+ * (unnormalised) belief of an update and the planner's tree shape are
+ * bit-identical for every setting; quantities that pass through a belief's
+ * mass or another whole-grid sum (normalised beliefs, Q-values of a belief,
+ * the default-order planner's bounds and rewards) are equal to rounding where
+ * a setting changes the association of that sum.
+ *  PP2_TUNE_CELLS_PER_LANE  1, 2 or 4 (default 4).  The workgroup partials of
+ *                           the mass cover other cells at each setting, so
+ *                           normalised beliefs and the default-order planner's
+ *                           sums are equal to rounding; the raw belief,
+ *                           values and actions are bit-identical.  The coded
+ *                           model (below) is used at 4 only; the planner's
+ *                           expansion kernels exist for 4 and 1 and run as 1
+ *                           at 2.
  *  PP2_TUNE_NT_STREAMS      1 (default) = non-temporal loads of the
- *                           once-read T/C streams (loop and sweep kernels,
- *                           CPT 4): -8 % time per loop step measured
+ *                           once-read T/C streams (loop and sweep kernels at
+ *                           4 cells per lane, the dense Q kernel): -8 % time
+ *                           per loop step measured.  Bit-identical either way.
  *  PP2_TUNE_CODED_MODEL     1 (default) = loop step and MDP sweep read the
  *                           dictionary-coded model (pp2_model_dict_info)
  *                           when one exists, and FIB sweeps skip the T

@@ -970,7 +970,9 @@ hipError_t launch_expand(hipStream_t st, const Geom& g, int cpt, PlaneSet T,
                          const float* b, PlaneSet R, PlaneSet L, PlaneSet F,
                          PlaneSet P, float* rpartials, float* spartials,
                          float* rewards_out, float* stats_out) {
-  const int tiles = cells_grid(g, cpt);
+  // the grid of the instantiation that runs: <4> at 4 cells per lane, else <1>
+  // (2 has none); the partial buffers hold cells_grid(g, 1) tiles
+  const int tiles = cells_grid(g, cpt == 4 ? 4 : 1);
   switch (cpt) {
     case 4:
       hipLaunchKernelGGL(k_expand_pred<4>, dim3(tiles), dim3(kBlock), 0, st, g, T, b, R, P, rpartials);
@@ -990,7 +992,7 @@ hipError_t launch_expand(hipStream_t st, const Geom& g, int cpt, PlaneSet T,
 hipError_t launch_belief_dots(hipStream_t st, const Geom& g, int cpt, const float* b,
                               PlaneSet F, float* partials, float* out, const float* mass,
                               float* mass_out) {
-  const int tiles = cells_grid(g, cpt);
+  const int tiles = cells_grid(g, cpt == 4 ? 4 : 1);  // as launch_expand
   if (cpt == 4)
     hipLaunchKernelGGL(k_belief_dots<4>, dim3(tiles), dim3(kBlock), 0, st, g, b, F, partials);
   else

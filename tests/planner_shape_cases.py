@@ -279,9 +279,9 @@ ALL = [(H, W) for H, W, _ in SHAPES]
 
 # reference order (bit for bit): (H, W, belief, lower_bound_mode, following
 # steps, switches).  switches: environment variables of the planner, plus
-# "fc_walk" (pp2_debug_fc_walk's argument), "coded" (TUNE_CODED_MODEL),
-# "off_support" (upload off_support_model) and "pbvi_ties" (pbvi_ties_of for
-# pbvi_of).
+# "fc_walk" (pp2_debug_fc_walk's argument), "coded" (TUNE_CODED_MODEL), "cpt"
+# (pp2_set_cells_per_lane), "off_support" (upload off_support_model) and
+# "pbvi_ties" (pbvi_ties_of for pbvi_of).
 REF_CASES = []
 for _hw in ALL:
     REF_CASES.append((*_hw, "uniform", 0, 1 if _hw == LARGEST else 3, {}))
@@ -305,6 +305,11 @@ for _hw in ((33, 65), (63, 131)):
 # for the off-support model only -- on the walked chains and the chain sets)
 for _hw in ((33, 65), (63, 131)):
     REF_CASES.append((*_hw, "uniform", 0, 3, {"off_support": 1}))
+# (below 4 cells per lane no coded model is active, whatever TUNE_CODED_MODEL
+# says: tree_sparse_t and the planner's host caches on such a context --
+# tuning_cases.TUNING)
+REF_CASES.append((33, 65, "uniform", 0, 3, {"cpt": 1}))
+REF_CASES.append((63, 131, "uniform", 0, 3, {"cpt": 2}))
 
 # default order (rel 1e-5 against the fp64-accumulating oracle): step 0 with
 # ONE expansion -- with more, the next node to expand is a comparison of

@@ -51,9 +51,11 @@ def context(P, H, W, sw, host_model):
             assert np.array_equal(ctx.model_download()[0].reshape(T.shape), T)
         if "coded" in sw:
             ctx.set_tuning(ctx.TUNE_CODED_MODEL, int(sw["coded"]))
-            assert ctx.model_dict_info()[1] == bool(sw["coded"])
-        else:
-            assert ctx.model_dict_info()[1]
+        if "cpt" in sw:
+            ctx.set_cells_per_lane(int(sw["cpt"]))
+        # the coded model is active at 4 cells per lane only
+        assert ctx.model_dict_info()[1] == (bool(sw.get("coded", 1)) and
+                                            int(sw.get("cpt", 4)) == 4)
         ctx.fib_solve(max_sweeps=40)
     except BaseException:
         ctx.close()

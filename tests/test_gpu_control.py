@@ -5,7 +5,8 @@ pp2_mdp_control; kernels in csrc/pp2_control.hip).
   pp2_belief_get (ties, zeros, padding, unnormalised stored beliefs).
 * QMDP on a one-hot belief is the Bellman backup of that cell, so it is held
   bit for bit to the library's own next sweep (values and first-minimum
-  actions).
+  actions), itself held to the oracle's sweep; with the coded model off, the
+  dense k_control_q at both settings of PP2_TUNE_NT_STREAMS as well.
 * On spread beliefs q is held to the fp64 reference
   (synthetic.control_reference) within the project's parity budget, rel 1e-5:
   every term b * Q is >= 0, so there is no cancellation, and an fp32 sum of n
@@ -42,6 +43,21 @@ def make_ctx(pp2, grid, goal, cpt=4):
     ctx.set_cells_per_lane(cpt)
     ctx.model_generate()
     return ctx
+
+
+# which Q kernel a case runs: the coded one (the default), or with the coded
+# model off the dense k_control_q<true> / k_control_q<false>
+# (PP2_TUNE_NT_STREAMS 1 / 0; the sweeps then run k_mdp_sweep<4, nt>)
+Q_KERNELS = ["coded", "dense_nt1", "dense_nt0"]
+
+
+def choose_q_kernel(ctx, kernel):
+    if kernel == "coded":
+        assert ctx.model_dict_info()[1]
+        return
+    ctx.set_tuning(ctx.TUNE_CODED_MODEL, 0)
+    ctx.set_tuning(ctx.TUNE_NT_STREAMS, int(kernel[-1]))
+    assert not ctx.model_dict_info()[1]
 
 
 def load_grid(name):
@@ -148,14 +164,16 @@ def onehot_cells(grid, rng):
     return cells
 
 
+@pytest.mark.parametrize("kernel", Q_KERNELS)
 @pytest.mark.parametrize("name", LOOP_MAPS + ["synth_97x131"])
-def test_qmdp_one_hot_is_the_next_sweep(pp2, name):
+def test_qmdp_one_hot_is_the_next_sweep(pp2, oracle, name, kernel):
     grid, goal = load_grid(name)
     H, W = grid.shape
     n = H * W
     cells = onehot_cells(grid, np.random.default_rng(7))
     cells.append(goal[1] * W + goal[0])
     with make_ctx(pp2, grid, goal) as ctx:
+        choose_q_kernel(ctx, kernel)
         ctx.mdp_reset()
         ctx.mdp_sweep(7)
         got = []
@@ -173,6 +191,13 @@ def test_qmdp_one_hot_is_the_next_sweep(pp2, name):
     for c, (a, v) in zip(cells, got):
         assert a == A[c], (name, c, a, A[c])
         assert bits(v)[0] == bits(J[c])[0], (name, c, v, J[c])
+    # and that sweep is the oracle's eighth
+    T, Cc = oracle.model_mdp(grid, goal)
+    Jo = np.zeros(n, np.float32)
+    for _ in range(8):
+        Jo, Ao = oracle.mdp_sweep(H, W, GAMMA, T, Cc, Jo)
+    np.testing.assert_array_equal(bits(J), bits(Jo))
+    np.testing.assert_array_equal(A, Ao)
 
 
 # ------------------------------------------------ 3. QMDP, spread beliefs
@@ -192,8 +217,9 @@ def check_q(ctx, q64, what):
     return clear
 
 
+@pytest.mark.parametrize("kernel", Q_KERNELS)
 @pytest.mark.parametrize("which", ["J7", "solved"])
-def test_qmdp_spread_beliefs_against_fp64(pp2, which):
+def test_qmdp_spread_beliefs_against_fp64(pp2, which, kernel):
     from path_planning_2d_amd import synthetic as S
     clear = 0
     for name in GOLDEN_MAPS:
@@ -202,6 +228,7 @@ def test_qmdp_spread_beliefs_against_fp64(pp2, which):
         m = golden("model", name)
         bt = golden("belief", name)
         with make_ctx(pp2, grid, goal) as ctx:
+            choose_q_kernel(ctx, kernel)
             if which == "J7":
                 ctx.mdp_reset()
                 ctx.mdp_sweep(7)

@@ -156,7 +156,7 @@ def test_fib_bit_exact(pp2, oracle, name):
     np.testing.assert_array_equal(got, g["alphas"])
 
 
-@pytest.mark.parametrize("cpt", [1, 4])
+@pytest.mark.parametrize("cpt", [1, 2, 4])
 def test_loop_step_matches_separate_ops(pp2, oracle, cpt):
     """The fused north-star step == belief update + Bellman sweep."""
     name = "tile64_sparse_map_100x40"
@@ -236,7 +236,7 @@ def test_errors_surface_as_exceptions(pp2):
 
 
 @pytest.mark.parametrize("block", [1, 2, 5, 8])
-@pytest.mark.parametrize("cpt", [1, 4])
+@pytest.mark.parametrize("cpt", [1, 2, 4])
 def test_loop_normalisation_blocks(pp2, oracle, block, cpt):
     """PP2_TUNE_NORM_BLOCK: the stored belief is divided by its exact mass
     every `block` steps (x 2^96, exact) and by 1 in between.  Over the 64-step

@@ -245,11 +245,15 @@ def test_grouped_context_rejects_per_context_stepping():
             grp.shards[0].loop_step(0, 0)
 
 
-def test_rccl_single_rank_pipeline():
+@pytest.mark.parametrize("comm_stream", [0, 1])
+def test_rccl_single_rank_pipeline(comm_stream):
     """The RCCL shard path on one GPU: a full-grid shard context with a
-    1-rank communicator runs the sharded loop pipeline -- comm stream, events,
-    asynchronous all-reduce of the mass, lagged normalisation, 8-deep
-    extended-domain views (neighbour transfers aside, which need 2 GPUs)."""
+    1-rank communicator runs the sharded loop pipeline -- asynchronous
+    all-reduce of the mass, lagged normalisation, 8-deep extended-domain
+    views (neighbour transfers aside, which need 2 GPUs).  With
+    PP2_TUNE_COMM_STREAM 0 every RCCL call is issued on the context's own
+    stream; with 1 on the dedicated comm stream, entered and left through
+    events (comm_enter / comm_leave)."""
     import path_planning_2d_amd as P
     from path_planning_2d_amd import synthetic as S
     name = "sparse_map_100x40"
@@ -261,6 +265,7 @@ def test_rccl_single_rank_pipeline():
     with P.GridContext(grid, goal, gamma=float(GAMMA)) as ref, \
             P.GridContext(grid, goal, gamma=float(GAMMA), rows=(0, H)) as sh:
         sh.shard_comm_init(P.GridContext.rccl_unique_id(), 1, 0)
+        sh.set_tuning(sh.TUNE_COMM_STREAM, comm_stream)
         for c in (ref, sh):
             c.model_generate()
             c.belief_set(b0)
