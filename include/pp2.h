@@ -1048,6 +1048,95 @@ int pp2_path_info(pp2_ctx* ctx, int* valid, int* rounds, int* launches, int* pol
 #define PP2_TABLE_PATH 1
 int pp2_episodes_set_action_table(pp2_episodes* ep, int table);
 
+/* ---------------------------------------------------------------- policy evaluation
+ * The exact outcome fields of a fixed action table: for a robot that knows
+ * its cell, follows table pi and moves in a given world, per start cell the
+ * expected discounted cost G, the probability P of reaching the goal within
+ * the horizon and the expected number of steps N -- the fully observed
+ * counterparts of an episode's cost, status == 1 and steps, on the same cost
+ * scale, for every start cell at once and without sampling.  The recurrence is
+ * the reference's cudaOneStepPolicyEvaluation (src/mdp/
+ * path_planning_2d_cuda.cu:266-306) with an absorbing goal, run for a fixed
+ * horizon; P and N ride along on the raw T.
+ *
+ * Inputs.  ctx holds the believed map and pi.  world holds the model the
+ * robot moves in (NULL: ctx itself): unsharded, with a model, on ctx's
+ * device and of ctx's geometry (PP2_EINVAL, as pp2_episodes_set_world), its
+ * gamma equal to ctx's as fp32 bits (PP2_EINVAL: the world's coded sweep rows
+ * hold fl(gamma * T) for its own gamma, so one gamma keeps both routes on the
+ * same operands).  T_w and C_w are the world's planes as pp2_model_download
+ * returns them; the goal is the world's goal cell, and a goal off the grid
+ * means there is none.  pi is
+ *   PP2_TABLE_MDP   the context's A as it stands when the call is enqueued
+ *                   (all zeros after pp2_mdp_reset, which is valid),
+ *   PP2_TABLE_PATH  A_path (PP2_ESTATE without a valid field),
+ *   PP2_TABLE_USER  the table last given to pp2_policy_set_table (PP2_ESTATE
+ *                   if none was given).
+ *
+ * Start planes: G_0 = N_0 = +0 everywhere; P_0 = 1.0f at the goal, +0 elsewhere.
+ * Step k = 1 .. horizon, for every grid cell x, with u = pi[x] and
+ * off_i = (i % 3 - 1, i / 3 - 1); a neighbour off the grid reads +0:
+ *   x is the goal:  G_k = +0, P_k = 1.0f, N_k = +0 (absorbing, as episode
+ *                   step 6);
+ *   otherwise:      g = C_w[x][u];
+ *                   for i = 0..8: g = fmaf(fl(gamma * T_w[x][u][i]), G_{k-1}(x + off_i), g)
+ *                     (pp2_mdp_sweep's arithmetic for the one action u)
+ *                   p = +0;
+ *                   for i = 0..8: p = fmaf(T_w[x][u][i], P_{k-1}(x + off_i), p)
+ *                   n = 1.0f;
+ *                   for i = 0..8: n = fmaf(T_w[x][u][i], N_{k-1}(x + off_i), n)
+ * All arithmetic is fp32 and flush-to-zero (subnormal operands read as zero,
+ * subnormal results are flushed).  Nothing but the goal is special-cased:
+ * occupied cells, cells where the table says 4 and a true cell that the
+ * believed map holds occupied all follow the arithmetic.  The outputs are
+ * G_H, P_H and N_H as [H*W] arrays.
+ *
+ * Routes.  Each step is a pure function of the previous planes, so tiling,
+ * the steps a launch runs and redundant ring computation cannot change a bit:
+ * both routes return identical bits.
+ *   PP2_POLICY_PLANES  one launch per step from the world's dense T and C
+ *                      planes; any model, uploaded ones without a dictionary
+ *                      included.  block is ignored.
+ *   PP2_POLICY_TILES   the world's dictionary-coded model, a tile of the three
+ *                      planes kept in LDS with a ring `block` cells deep,
+ *                      `block` steps per launch (0: default_block).
+ *                      PP2_ESTATE unless the world's coded model is active with
+ *                      factored rows (pp2_model_dict_info) and every T row of
+ *                      its dictionary sums to at most 1 + 2^-20 (generated
+ *                      models always qualify): the route drops the T == +0
+ *                      terms, which is exact while every value is finite.
+ *   PP2_POLICY_AUTO    TILES when admissible, else PLANES.
+ *
+ * pp2_policy_set_table: table is [H*W], every entry <= 8 (else PP2_EINVAL,
+ * the earlier table kept); copied before the call returns.  NULL drops it.
+ * pp2_policy_evaluate: horizon in 1 .. 65536, block in 0 .. max_block; an
+ * unknown table or route or anything out of range is PP2_EINVAL.  A row
+ * shard, RCCL rank or group member, as ctx or as world: PP2_ESTATE.
+ * Asynchronous on ctx's stream: it first settles pending resident launches
+ * of both contexts and re-checks the models (as pp2_episodes_run), and orders
+ * itself against the world's stream with one event each way when the streams
+ * differ.  Planes and scratch are allocated by the first evaluation
+ * (PP2_ENOMEM leaves the context usable) and freed by pp2_destroy.  The
+ * result is a snapshot: later map updates, sweeps or solves do not invalidate
+ * it, and the next evaluation replaces it.  No belief, value, action table or
+ * alpha vector of either context is written.
+ * pp2_policy_get: G, P and N as [H*W] arrays, any may be NULL; synchronises.
+ * PP2_ESTATE before any evaluation.
+ * pp2_policy_info: what the result was computed from (valid, table, horizon,
+ * the route taken, steps per launch, kernels launched) and the TILES route's
+ * compile-time constants.  Any pointer may be NULL. */
+#define PP2_TABLE_USER 2
+#define PP2_POLICY_AUTO   0
+#define PP2_POLICY_PLANES 1
+#define PP2_POLICY_TILES  2
+int pp2_policy_set_table(pp2_ctx* ctx, const uint8_t* table);
+int pp2_policy_evaluate(pp2_ctx* ctx, pp2_ctx* world, int table, int horizon, int route,
+                        int block);
+int pp2_policy_get(pp2_ctx* ctx, float* G, float* P, float* N);
+int pp2_policy_info(pp2_ctx* ctx, int* valid, int* table, int* horizon, int* route_taken,
+                    int* block, int* launches, int* tile_rows, int* tile_cols,
+                    int* default_block, int* max_block);
+
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):
  *  - one process per GPU: RCCL (pp2_rccl_unique_id / pp2_shard_comm_init);

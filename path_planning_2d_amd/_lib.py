@@ -151,6 +151,10 @@ SIGNATURES = {
     "pp2_path_control": [_vp, _u8p, _f32p, C.POINTER(C.c_int32)],
     "pp2_path_trace": [_vp, C.c_int32, C.POINTER(C.c_int32), C.c_int, _i32p, _f32p],
     "pp2_path_info": [_vp, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "pp2_policy_set_table": [_vp, _u8p],
+    "pp2_policy_evaluate": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int],
+    "pp2_policy_get": [_vp, _f32p, _f32p, _f32p],
+    "pp2_policy_info": [_vp] + [_i32p] * 10,
     "pp2_episodes_set_action_table": [_vp, C.c_int],
     "pp2_shard_group_create": [C.POINTER(_vp), C.POINTER(_vp), C.c_int],
     "pp2_shard_group_destroy": [_vp],

@@ -437,6 +437,59 @@ class GridContext:
         out["valid"] = bool(out["valid"])
         return out
 
+    # ------------------------------------------------------------ policy evaluation
+    _POLICY_TABLES = {"mdp": 0, "path": 1, "user": 2}
+    _POLICY_ROUTES = {"auto": 0, "planes": 1, "tiles": 2}
+
+    def policy_set_table(self, table):
+        """The ``"user"`` table of ``policy_evaluate``: H x W actions, every
+        entry <= 8 (pp2_policy_set_table); ``None`` drops it."""
+        if table is None:
+            call("pp2_policy_set_table", self._h, None)
+            return
+        t = np.ascontiguousarray(table, dtype=np.uint8)
+        if t.size != self.rows * self.width:
+            raise ValueError(f"table has {t.size} entries, the grid {self.rows * self.width}")
+        call("pp2_policy_set_table", self._h, _u8(t))
+
+    def policy_evaluate(self, horizon: int, table="mdp", world=None, route="auto", block: int = 0):
+        """Enqueue the exact outcome fields of an action table over ``horizon``
+        steps (pp2_policy_evaluate): ``table`` is ``"mdp"`` (A), ``"path"``
+        (A_path) or ``"user"``; ``world`` the context whose model the robot
+        moves in (None: this one); ``route`` ``"auto"``, ``"planes"`` or
+        ``"tiles"``; ``block`` the steps per launch of the tiles route (0: the
+        default).  ``policy_get`` returns the result."""
+        if isinstance(table, str):
+            if table not in self._POLICY_TABLES:
+                raise ValueError(f"unknown action table {table!r}")
+            table = self._POLICY_TABLES[table]
+        if isinstance(route, str):
+            if route not in self._POLICY_ROUTES:
+                raise ValueError(f"unknown route {route!r}")
+            route = self._POLICY_ROUTES[route]
+        call("pp2_policy_evaluate", self._h, world._h if world is not None else None,
+             int(table), int(horizon), int(route), int(block))
+
+    def policy_get(self):
+        """(G, P, N) as H x W float32 arrays: expected discounted cost, goal
+        probability within the horizon and expected steps per start cell, of
+        the last ``policy_evaluate``.  Synchronises."""
+        out = [np.empty((self.rows, self.width), np.float32) for _ in range(3)]
+        call("pp2_policy_get", self._h, *[_f32(a) for a in out])
+        return tuple(out)
+
+    def policy_info(self):
+        """dict: valid, table, horizon, route_taken, block and launches of the
+        last evaluation; tile_rows, tile_cols, default_block, max_block of the
+        tiles route."""
+        v = [C.c_int() for _ in range(10)]
+        call("pp2_policy_info", self._h, *[C.byref(x) for x in v])
+        keys = ("valid", "table", "horizon", "route_taken", "block", "launches", "tile_rows",
+                "tile_cols", "default_block", "max_block")
+        out = {k: x.value for k, x in zip(keys, v)}
+        out["valid"] = bool(out["valid"])
+        return out
+
     # ------------------------------------------------------------ FIB
     def fib_reset(self):
         call("pp2_fib_reset", self._h)

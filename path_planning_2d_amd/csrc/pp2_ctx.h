@@ -288,6 +288,19 @@ struct pp2_ctx {
   bool path_cached = false;        // the host copies below are the valid field's
   std::vector<float> h_path_D;     // [H * W] (pp2_path_trace)
   std::vector<uint8_t> h_path_A;
+
+  // Policy evaluation (pp2_policy.cpp), allocated by the first
+  // pp2_policy_evaluate: two sides of {G, P, N} planes of [rows * width] and
+  // the TILES route's class bytes; the USER table by pp2_policy_set_table.
+  // The result is the side pol_side, a snapshot of what pol_* describe.
+  float* pol_planes = nullptr;
+  uint8_t* pol_cls = nullptr;
+  uint8_t* pol_user = nullptr;     // device copy, [rows * width]
+  bool pol_user_set = false;
+  hipEvent_t pol_ev_world = nullptr, pol_ev_run = nullptr;  // a world on another stream
+  bool pol_valid = false;
+  int pol_side = 0, pol_table = 0, pol_horizon = 0, pol_route = 0, pol_block = 0;
+  int pol_launches = 0;            // kernels of the last evaluation
 };
 
 namespace pp2rt {
@@ -374,6 +387,7 @@ std::string join(const char* dir, const char* name);
 
 void pbvi_free(pp2_ctx* c);
 void path_free(pp2_ctx* c);  // the shortest-path field's buffers (pp2_path.cpp)
+void policy_free(pp2_ctx* c);  // the policy evaluator's buffers (pp2_policy.cpp)
 // The context's PBVI alpha vectors (device rows of ld floats, Sp rows); ESTATE if none.
 int pbvi_alphas(pp2_ctx* c, const float** alpha, int* S, int* Sp, int* ld);
 // ... and their actions (device, [S]); ESTATE if none.
