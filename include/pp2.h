@@ -1137,6 +1137,90 @@ int pp2_policy_info(pp2_ctx* ctx, int* valid, int* table, int* horizon, int* rou
                     int* block, int* launches, int* tile_rows, int* tile_cols,
                     int* default_block, int* max_block);
 
+/* ---------------------------------------------------------------- occupancy
+ * The forward occupancy of an action table: where a robot that knows its
+ * cell, follows table pi and moves in a given world is after k steps from a
+ * start distribution b0, which cells it passes through and how often, and how
+ * the probability of having arrived grows step by step.  The adjoint of the
+ * policy evaluation above: with P_H and N_H of pp2_policy_evaluate for the
+ * same table, world and horizon H,
+ *   <b0, P_H> = D_H(goal) = curve[H]   and   <b0, N_H> = sum over cells of V_H
+ * in exact arithmetic (the fp32 results agree to the roundings of H steps).
+ *
+ * Inputs.  ctx, world (NULL: ctx itself), the table (PP2_TABLE_MDP / _PATH /
+ * _USER) and their conditions are pp2_policy_evaluate's: the same geometry,
+ * device and gamma-bits checks (PP2_EINVAL), the same PP2_ESTATE cases and the
+ * same shard refusal.  The goal is the world's goal; a goal off the grid
+ * means there is none.  off_i = (i % 3 - 1, i / 3 - 1), and T_w is the
+ * world's T as pp2_model_download returns it.
+ * b0 is [H*W] floats, copied before the call returns.  Every entry must
+ * satisfy 0 <= e <= 1.0f and must not be NaN, else PP2_EINVAL, and the
+ * earlier result stays untouched; -0 and subnormals are read as +0.  b0 need
+ * not sum to 1.
+ *
+ * Start planes: D_0 = b0 after that canonicalisation, V_0 = +0;
+ * curve[0] = D_0(goal), or +0 if there is no goal.
+ * Step k = 1 .. horizon: let S(x) = D_{k-1}(x) for x off the goal and
+ * S(goal) = +0; a source off the grid reads +0.  For every grid cell y:
+ *   V_k(y) = V_{k-1}(y) + S(y)       (one fp32 add: the expected visits
+ *                                     before arrival; the goal holds +0)
+ *   d = D_{k-1}(y) if y is the goal, else +0;
+ *   for i = 0..8, with x = y - off_i:
+ *     d = fmaf(T_w[x][pi[x]][i], S(x), d)
+ *       (the mass that source x sends to its neighbour i, which is y; the
+ *        goal absorbs: it keeps its mass and sends none)
+ *   D_k(y) = d
+ *   curve[k] = D_k(goal)
+ * All arithmetic is fp32 and flush-to-zero, as in the evaluator.  Nothing but
+ * the goal is special-cased: occupied cells, mass placed on occupied cells
+ * and table entries of 4 all follow the arithmetic.  The outputs are D_H
+ * [H*W], V_H [H*W] and curve [horizon + 1].
+ *
+ * Routes.  Each step is a pure function of the previous planes, so tiling,
+ * the steps a launch runs and redundant ring computation cannot change a bit:
+ * both routes return identical bits.
+ *   PP2_OCC_PLANES  any model, uploaded ones without a dictionary included:
+ *                   the nine gather weights of every cell, T_w[x][pi[x]][i]
+ *                   with x = y - off_i (+0 for a source off the grid or the
+ *                   goal), are materialised once per evaluation into nine
+ *                   [H*W] planes; then one launch per step.  block is ignored.
+ *   PP2_OCC_TILES   the world's dictionary-coded model, a tile of D kept in
+ *                   LDS with a ring `block` cells deep, `block` steps per
+ *                   launch (0: default_block), the gather weights and V of a
+ *                   thread's cells in registers across a launch's steps.
+ *                   PP2_ESTATE unless PP2_POLICY_TILES would be admitted in
+ *                   the same world (coded model active with factored rows,
+ *                   every dictionary T row summing to at most 1 + 2^-20): the
+ *                   route multiplies by +0 where the definition skips a
+ *                   source, which is exact while every value is finite --
+ *                   D(y) <= sum(b0) * (1 + 2^-20)^horizon.
+ *   PP2_OCC_AUTO    TILES when admissible, else PLANES.
+ *
+ * pp2_occupancy_evaluate: horizon in 1 .. 65536, block in 0 .. max_block; a
+ * NULL b0, an unknown table or route or anything out of range is PP2_EINVAL.
+ * Asynchronous on ctx's stream, with pp2_policy_evaluate's settling, model
+ * re-check and stream ordering (one event each way when the world's stream
+ * differs).  Planes and scratch are allocated on first use (PP2_ENOMEM leaves
+ * the context usable) and freed by pp2_destroy.  The result is a snapshot
+ * that the next occupancy evaluation replaces; its storage is separate from
+ * the policy evaluation's, so neither call disturbs the other's *_get.  No
+ * belief, value, action table or alpha vector of either context is written.
+ * pp2_occupancy_get: D and V as [H*W], curve as [horizon + 1] of the last
+ * evaluation, any may be NULL; synchronises.  PP2_ESTATE before any evaluation.
+ * pp2_occupancy_info: as pp2_policy_info.  launches counts the kernels of the
+ * last evaluation: the start planes, the class bytes (TILES) or the weight
+ * planes (PLANES), and ceil(horizon / block) step launches (block = 1 under
+ * PLANES).  Any pointer may be NULL. */
+#define PP2_OCC_AUTO   0
+#define PP2_OCC_PLANES 1
+#define PP2_OCC_TILES  2
+int pp2_occupancy_evaluate(pp2_ctx* ctx, pp2_ctx* world, int table, const float* b0,
+                           int horizon, int route, int block);
+int pp2_occupancy_get(pp2_ctx* ctx, float* D, float* V, float* curve);
+int pp2_occupancy_info(pp2_ctx* ctx, int* valid, int* table, int* horizon, int* route_taken,
+                       int* block, int* launches, int* tile_rows, int* tile_cols,
+                       int* default_block, int* max_block);
+
 /* ---------------------------------------------------------------- shards
  * Two transports for row shards (no reference counterpart):
  *  - one process per GPU: RCCL (pp2_rccl_unique_id / pp2_shard_comm_init);

@@ -155,6 +155,9 @@ SIGNATURES = {
     "pp2_policy_evaluate": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int],
     "pp2_policy_get": [_vp, _f32p, _f32p, _f32p],
     "pp2_policy_info": [_vp] + [_i32p] * 10,
+    "pp2_occupancy_evaluate": [_vp, _vp, C.c_int, _f32p, C.c_int, C.c_int, C.c_int],
+    "pp2_occupancy_get": [_vp, _f32p, _f32p, _f32p],
+    "pp2_occupancy_info": [_vp] + [_i32p] * 10,
     "pp2_episodes_set_action_table": [_vp, C.c_int],
     "pp2_shard_group_create": [C.POINTER(_vp), C.POINTER(_vp), C.c_int],
     "pp2_shard_group_destroy": [_vp],

@@ -490,6 +490,54 @@ class GridContext:
         out["valid"] = bool(out["valid"])
         return out
 
+    # ------------------------------------------------------------ occupancy
+    def occupancy_evaluate(self, horizon: int, b0=None, table="mdp", world=None, route="auto",
+                           block: int = 0):
+        """Enqueue the forward occupancy of an action table over ``horizon``
+        steps from the start distribution ``b0`` (pp2_occupancy_evaluate): H x W
+        entries in [0, 1], ``None`` for the context's belief (``belief_get``).
+        ``table``, ``world``, ``route`` and ``block`` as in ``policy_evaluate``.
+        ``occupancy_get`` returns the result."""
+        if isinstance(table, str):
+            if table not in self._POLICY_TABLES:
+                raise ValueError(f"unknown action table {table!r}")
+            table = self._POLICY_TABLES[table]
+        if isinstance(route, str):
+            if route not in self._POLICY_ROUTES:
+                raise ValueError(f"unknown route {route!r}")
+            route = self._POLICY_ROUTES[route]
+        if b0 is None:
+            b0 = self.belief_get()
+        b = np.ascontiguousarray(b0, dtype=np.float32)
+        if b.size != self.rows * self.width:
+            raise ValueError(f"b0 has {b.size} entries, the grid {self.rows * self.width}")
+        call("pp2_occupancy_evaluate", self._h, world._h if world is not None else None,
+             int(table), _f32(b), int(horizon), int(route), int(block))
+
+    def occupancy_get(self):
+        """(D, V, curve) of the last ``occupancy_evaluate``: the distribution
+        after the horizon and the expected visits before arrival as H x W
+        float32 arrays, and the mass at the goal after step 0 .. horizon.
+        Synchronises."""
+        horizon = self.occupancy_info()["horizon"]
+        D = np.empty((self.rows, self.width), np.float32)
+        V = np.empty((self.rows, self.width), np.float32)
+        curve = np.empty(horizon + 1, np.float32)
+        call("pp2_occupancy_get", self._h, _f32(D), _f32(V), _f32(curve))
+        return D, V, curve
+
+    def occupancy_info(self):
+        """dict: valid, table, horizon, route_taken, block and launches of the
+        last occupancy evaluation; tile_rows, tile_cols, default_block,
+        max_block of the tiles route."""
+        v = [C.c_int() for _ in range(10)]
+        call("pp2_occupancy_info", self._h, *[C.byref(x) for x in v])
+        keys = ("valid", "table", "horizon", "route_taken", "block", "launches", "tile_rows",
+                "tile_cols", "default_block", "max_block")
+        out = {k: x.value for k, x in zip(keys, v)}
+        out["valid"] = bool(out["valid"])
+        return out
+
     # ------------------------------------------------------------ FIB
     def fib_reset(self):
         call("pp2_fib_reset", self._h)

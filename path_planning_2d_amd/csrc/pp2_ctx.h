@@ -301,6 +301,25 @@ struct pp2_ctx {
   bool pol_valid = false;
   int pol_side = 0, pol_table = 0, pol_horizon = 0, pol_route = 0, pol_block = 0;
   int pol_launches = 0;            // kernels of the last evaluation
+
+  // Forward occupancy (pp2_occupancy.cpp), allocated by the
+  // first pp2_occupancy_evaluate: two sides of {D, V} planes of [rows * width],
+  // the canonical b0 (device, and its pinned staging copy with the event of
+  // its upload), the curve (65537 floats), and per route the nine weight
+  // planes (PLANES) or the class bytes (TILES).  The result is the side
+  // occ_side and occ_curve, a snapshot of what occ_* describe; nothing here is
+  // shared with the policy evaluator's result.
+  float* occ_planes = nullptr;
+  float* occ_wts = nullptr;
+  float* occ_b0 = nullptr;
+  float* occ_curve = nullptr;
+  uint8_t* occ_cls = nullptr;
+  float* occ_h_b0 = nullptr;
+  hipEvent_t occ_ev_b0 = nullptr;
+  hipEvent_t occ_ev_world = nullptr, occ_ev_run = nullptr;  // a world on another stream
+  bool occ_valid = false;
+  int occ_side = 0, occ_table = 0, occ_horizon = 0, occ_route = 0, occ_block = 0;
+  int occ_launches = 0;            // kernels of the last evaluation
 };
 
 namespace pp2rt {
@@ -388,6 +407,11 @@ std::string join(const char* dir, const char* name);
 void pbvi_free(pp2_ctx* c);
 void path_free(pp2_ctx* c);  // the shortest-path field's buffers (pp2_path.cpp)
 void policy_free(pp2_ctx* c);  // the policy evaluator's buffers (pp2_policy.cpp)
+// The evaluator's shard refusal and its TILES admission (pp2_policy.cpp), for
+// the forward occupancy, which has the same demands on the context and the world.
+bool policy_sharded(const pp2_ctx* c);
+bool policy_tiles_ok(const pp2_ctx* w);
+void occupancy_free(pp2_ctx* c);  // the forward occupancy's buffers (pp2_occupancy.cpp)
 // The context's PBVI alpha vectors (device rows of ld floats, Sp rows); ESTATE if none.
 int pbvi_alphas(pp2_ctx* c, const float** alpha, int* S, int* Sp, int* ld);
 // ... and their actions (device, [S]); ESTATE if none.

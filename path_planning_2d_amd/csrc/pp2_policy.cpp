@@ -72,6 +72,9 @@ pp2::PolicyPlanes side(const pp2_ctx* c, int s) {
 }  // namespace
 
 namespace pp2rt {
+bool policy_sharded(const pp2_ctx* c) { return sharded(c); }
+bool policy_tiles_ok(const pp2_ctx* w) { return tiles_ok(w); }
+
 void policy_free(pp2_ctx* c) {
   policy_release(c);
   if (c->pol_user) (void)hipFree(c->pol_user);

@@ -1777,6 +1777,7 @@ int pp2_destroy(pp2_ctx* c) {
   if (c->ctl_host) (void)hipHostFree(c->ctl_host);
   path_free(c);
   policy_free(c);
+  occupancy_free(c);
   if (c->code_alloc) (void)hipFree(c->code_alloc);
   resident_free(c);
   if (c->res_host) (void)hipHostFree(c->res_host);
