@@ -1086,7 +1086,9 @@ int pp2_episodes_set_action_table(pp2_episodes* ep, int table);
  *                   n = 1.0f;
  *                   for i = 0..8: n = fmaf(T_w[x][u][i], N_{k-1}(x + off_i), n)
  * All arithmetic is fp32 and flush-to-zero (subnormal operands read as zero,
- * subnormal results are flushed).  Nothing but the goal is special-cased:
+ * subnormal results are flushed: a result is rounded to nearest even first and
+ * flushed if what the rounding gives is subnormal, so an exact value just
+ * below 2^-126 that rounds up to it stays).  Nothing but the goal is special-cased:
  * occupied cells, cells where the table says 4 and a true cell that the
  * believed map holds occupied all follow the arithmetic.  The outputs are
  * G_H, P_H and N_H as [H*W] arrays.

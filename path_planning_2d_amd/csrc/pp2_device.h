@@ -16,6 +16,21 @@ typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 constexpr int kBlock = 256;
 
+// Flush-to-zero as include/pp2.h defines it for the policy evaluator and the
+// occupancy: a subnormal operand reads as zero of its sign, and a result is
+// flushed after it has been rounded -- a value that rounds up to 2^-126
+// stays.  The hardware's flush mode decides on the unrounded value instead
+// (fmaf(1 - 2^-24, 2^-126, +0) returns +0 there), so pp2_policy.hip and
+// pp2_occupancy.hip are built with IEEE subnormals and flush here.
+__device__ __forceinline__ float ftz(float x) {
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x7f800000u) ? x : __uint_as_float(b & 0x80000000u);
+}
+// (a, b and c already flushed)
+__device__ __forceinline__ float fma_ftz(float a, float b, float c) {
+  return ftz(__builtin_fmaf(a, b, c));
+}
+
 template <int N, bool ALIGNED>
 __device__ __forceinline__ void ldv(const float* __restrict__ p, float (&v)[N]) {
   if constexpr (N == 4) {

@@ -171,6 +171,22 @@ inline DictProps dict_props(const float* dict, int E, int dict_row, float gamma)
   return p;
 }
 
+// Every T row of the dictionary sums to at most 1 + 2^-20 (the nine entries
+// added in fp64 in index order; a NaN entry fails): the TILES routes of the
+// policy evaluator and of the occupancy ask it of an uploaded model, so that P
+// stays below 2 and N below 2 * horizon over the 65536 steps a call may ask
+// for and every value they multiply by a dropped +0 is finite.  An empty
+// dictionary has no row that breaks it.
+inline bool dict_rows_bounded(const float* dict, int E, int dict_row) {
+  for (int e = 0; e < E; ++e)
+    for (int a = 0; a < 9; ++a) {
+      double s = 0.0;
+      for (int i = 0; i < 9; ++i) s += (double)dict[(size_t)e * dict_row + a * 10 + i];
+      if (!(s <= 1.0 + 0x1p-20)) return false;
+    }
+  return true;
+}
+
 // The context's switches and state flags that the predicates read.
 struct GateCtx {
   bool resident = true;     // PP2_TUNE_RESIDENT

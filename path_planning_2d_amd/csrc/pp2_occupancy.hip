@@ -26,6 +26,9 @@
 //    chain from its own value.  A weight that is +0 contributes
 //    fmaf(+0, v, acc) == acc: every v is finite and >= +0 under the route's
 //    admission and no accumulator is -0.
+// Flush-to-zero is the definition's, in code (pp2_device.h: ftz, fma_ftz; this
+// file is built with IEEE subnormals): the model's entries are flushed where
+// they are read, every result after its rounding; b0 arrives flushed.
 //
 // Lane = region column, row stride kS = 66 words: the nine LDS reads of a step
 // are at the same nine offsets for all 64 lanes of a wave, so each is 64
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_weights(Geom g, PlaneSet T,
     float w = 0.0f;
     if (src) {
       const int u = pi[(long long)yy * pis + xx];
-      w = T.p[(long long)yy * T.rs + (long long)(9 * u + i) * T.ps + xx];
+      w = ftz(T.p[(long long)yy * T.rs + (long long)(9 * u + i) * T.ps + xx]);
     }
     wts[(long long)i * n + cell] = w;
   }
@@ -105,13 +108,13 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_step(Geom g, const float* _
   const bool goal = x == gx && y == gy;
   const float dc = in.D[cell];
   float d = goal ? dc : 0.0f;
-  out.V[cell] = in.V[cell] + (goal ? 0.0f : dc);
+  out.V[cell] = ftz(in.V[cell] + (goal ? 0.0f : dc));
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     const int yy = y - (i / 3 - 1), xx = x - (i % 3 - 1);
     const bool src = yy >= 0 && yy < H && xx >= 0 && xx < W && !(xx == gx && yy == gy);
     const float s = src ? in.D[(long long)yy * W + xx] : 0.0f;
-    d = __builtin_fmaf(wts[(long long)i * n + cell], s, d);
+    d = fma_ftz(wts[(long long)i * n + cell], s, d);
   }
   out.D[cell] = d;
   if (goal) curve[k] = d;
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_tiles(
       const f4a r = *reinterpret_cast<const f4a*>(rfact + kResQR + 4 * tid);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (j < cOccSupN[u]) sRow[9 * tid + cOccSup[u][j]] = r[j];
+        if (j < cOccSupN[u]) sRow[9 * tid + cOccSup[u][j]] = ftz(r[j]);
     }
   }
   // both sides +0 and every class byte "off the grid": the pads, and the lanes
@@ -198,11 +201,11 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_tiles(
           const bool goal = (goal_m >> k) & 1u;
           const float dc = vi[li];
           float d = goal ? dc : 0.0f;
-          v[k] = v[k] + (goal ? 0.0f : dc);
+          v[k] = ftz(v[k] + (goal ? 0.0f : dc));
 #pragma unroll
           for (int i = 0; i < 9; ++i) {
             const float sv = i == 4 ? dc : vi[li - (i / 3 - 1) * kS - (i % 3 - 1)];
-            d = __builtin_fmaf(w[k][i], sv, d);
+            d = fma_ftz(w[k][i], sv, d);
           }
           vo[li] = d;
           // the goal's owner: the workgroup whose tile holds it

@@ -20,20 +20,13 @@ bool sharded(const pp2_ctx* c) {
   return c->nranks > 1 || c->group || c->comm || c->g.rows != c->g.grows || c->g.halo != 1;
 }
 
-// Every T row of the world's dictionary sums to at most 1 + 2^-20: P stays
-// below 2 and N below 2 * horizon over the 65536 steps a call may ask for,
-// so every value the TILES route multiplies by a dropped +0 is finite
-// (generated models: each row is a probability distribution).
+// Every T row of the world's dictionary sums to at most 1 + 2^-20
+// (pp2_dict_props.h: dict_rows_bounded; generated models: each row is a
+// probability distribution).
 bool rows_bounded(const pp2_ctx* w) {
   if (w->model_generated) return true;
   if (w->h_dict.size() != (size_t)w->dict_n * pp2::kDictRow) return false;
-  for (int e = 0; e < w->dict_n; ++e)
-    for (int a = 0; a < 9; ++a) {
-      double s = 0.0;
-      for (int i = 0; i < 9; ++i) s += (double)w->h_dict[(size_t)e * pp2::kDictRow + a * 10 + i];
-      if (!(s <= 1.0 + 0x1p-20)) return false;
-    }
-  return true;
+  return pp2::dict_rows_bounded(w->h_dict.data(), w->dict_n, pp2::kDictRow);
 }
 
 // the TILES route's demands on the world: the episodes' (check_episode_world)

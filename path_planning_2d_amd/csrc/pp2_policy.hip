@@ -24,6 +24,9 @@
 // are the dense ones.  Cells off the grid and the goal are classes too: all
 // weights +0 and the start values {+0, +0, +0} / {+0, 1, +0}, so they hold
 // their pinned values through the same arithmetic as every other cell.
+// Flush-to-zero is the definition's, in code (pp2_device.h: ftz, fma_ftz; this
+// file is built with IEEE subnormals): the model's entries are flushed where
+// they are read, every result after its rounding.
 //
 // Lane = region column (row stride kS = 66 words: a row access of the 64
 // lanes hits 64 banks, and columns -1 and 64 are the pad), wave w = region
@@ -78,21 +81,22 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_step(
   }
   const int u = pi[(long long)y * pis + x];
   const float* tp = T.p + (long long)y * T.rs + (long long)(9 * u) * T.ps + x;
-  float gv = C.p[(long long)y * C.rs + (long long)u * C.ps + x];
+  float gv = ftz(C.p[(long long)y * C.rs + (long long)u * C.ps + x]);
   float pv = 0.0f, nv = 1.0f;
+  gamma = ftz(gamma);
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     const int yy = y + i / 3 - 1, xx = x + i % 3 - 1;
     const bool on = yy >= 0 && yy < H && xx >= 0 && xx < W;
     const long long at = on ? (long long)yy * W + xx : cell;
-    const float t = tp[(long long)i * T.ps];
-    const float gt = gamma * t;
+    const float t = ftz(tp[(long long)i * T.ps]);
+    const float gt = ftz(gamma * t);
     const float gn = on ? in.G[at] : 0.0f;
     const float pn = on ? in.P[at] : 0.0f;
     const float nn = on ? in.N[at] : 0.0f;
-    gv = __builtin_fmaf(gt, gn, gv);
-    pv = __builtin_fmaf(t, pn, pv);
-    nv = __builtin_fmaf(t, nn, nv);
+    gv = fma_ftz(gt, gn, gv);
+    pv = fma_ftz(t, pn, pv);
+    nv = fma_ftz(t, nn, nv);
   }
   out.G[cell] = gv;
   out.P[cell] = pv;
@@ -141,12 +145,12 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_tiles(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool in_sup = j < cPolSupN[u];
-        qt[j] = in_sup ? t[j] : 0.0f;
-        qr[j] = in_sup ? r[j] : 0.0f;
+        qt[j] = in_sup ? ftz(t[j]) : 0.0f;
+        qr[j] = in_sup ? ftz(r[j]) : 0.0f;
         const int i = cPolSup[u][j];
         offs |= (uint32_t)(((i / 3 - 1) * kS + i % 3 - 1) & 0xff) << (8 * j);
       }
-      cn[0] = rows[kFactCT + 4 * tid];
+      cn[0] = ftz(rows[kFactCT + 4 * tid]);
       cn[2] = 1.0f;
       cn[3] = __uint_as_float(offs);
     } else if (tid == kPolicyClsGoal) {
@@ -207,9 +211,9 @@ __global__ __launch_bounds__(kPolicyThreads) void k_policy_tiles(
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int at = li + (int)(int8_t)(offs >> (8 * j));
-          gv = __builtin_fmaf(qt[j], vi[at], gv);
-          pv = __builtin_fmaf(qr[j], vi[pl + at], pv);
-          nv = __builtin_fmaf(qr[j], vi[2 * pl + at], nv);
+          gv = fma_ftz(qt[j], vi[at], gv);
+          pv = fma_ftz(qr[j], vi[pl + at], pv);
+          nv = fma_ftz(qr[j], vi[2 * pl + at], nv);
         }
         vo[li] = gv;
         vo[pl + li] = pv;

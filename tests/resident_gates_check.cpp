@@ -347,6 +347,56 @@ int main() {
       std::printf("FAIL plane scan / gamma bound\n");
     }
   }
+  // the row-sum rule of the evaluators' TILES routes: every T row sums to at
+  // most 1 + 2^-20 in fp64
+  {
+    auto bounded = [&](const char* name, const Dict& d, bool want) {
+      ++rows;
+      if (pp2::dict_rows_bounded(d.data(), (int)(d.size() / kRow), kRow) != want) {
+        ++failures;
+        std::printf("FAIL row sums, %s: want %d\n", name, (int)want);
+      }
+    };
+    // the last entry's action-6 row (support {3, 4, 6, 7}) as {0.5, 0.5, x, 0}
+    auto with_row = [&](float x) {
+      Dict d = clean();
+      float* r = &d[3 * kRow + 6 * 10];
+      for (int i = 0; i < 9; ++i) r[i] = 0.0f;
+      r[3] = 0.5f;
+      r[4] = 0.5f;
+      r[6] = x;
+      return d;
+    };
+    bounded("generated-like", clean(), true);
+    bounded("sum exactly 1", with_row(0.0f), true);
+    bounded("sum exactly 1 + 2^-20", with_row(0x1p-20f), true);
+    bounded("sum 1 + 2^-20 + 2^-43 (one fp64 step past the bound)", with_row(0x1p-20f + 0x1p-43f),
+            false);
+    bounded("sum 1 + 2^-19", with_row(0x1p-19f), false);
+    bounded("a NaN entry", with_row(nan), false);
+    bounded("an inf entry", with_row(inf), false);
+    {
+      Dict d = clean();  // sub-stochastic and all-zero rows
+      for (int a = 0; a < 9; ++a)
+        for (int i = 0; i < 9; ++i) {
+          d[1 * kRow + a * 10 + i] *= 0.5f;
+          d[2 * kRow + a * 10 + i] = 0.0f;
+        }
+      bounded("sub-stochastic and all-zero rows", d, true);
+    }
+    {
+      Dict d = with_row(0x1p-19f);  // the first entry's first row instead of the last's
+      Dict e = clean();
+      for (int i = 0; i < 9; ++i) e[i] = d[3 * kRow + 6 * 10 + i];
+      bounded("sum 1 + 2^-19 in the first row", e, false);
+    }
+    bounded("an empty dictionary", Dict(), true);
+    ++rows;
+    if (!pp2::dict_rows_bounded(nullptr, 0, kRow)) {
+      ++failures;
+      std::printf("FAIL row sums, no rows and no storage\n");
+    }
+  }
   std::printf("%d rows, %d failures\n", rows, failures);
   if (failures) return 1;
   std::printf("all rows hold\n");
